@@ -1,6 +1,17 @@
 """SdP-Net forward benchmark on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N --steps K --warmup W] [--config m|xl|xl_train] [--no-secondary]
+  python bench.py [--gpus N --steps K --warmup W] [--config m|xl|xl_train] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: set up, W warmup steps,
+K timed steps, the outputs if asked for, one JSON line (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds per timed step, ...).  --full adds
+the roofline, secondary and cpu_baseline measurements described at the end.
+
+--dump-outputs DIR writes what the timed path returned in its last timed step as
+float32 DIR/<name>.npy (forward: logits; xl_train: logits and loss; <name>_rank<r> when
+N > 1; a fixed seeded sample when an array would pass 64 MB in all).  Weights and inputs
+are seeded, so the same arguments give the same inputs in every run and two builds can
+be compared output for output.
 
 --gpus N > 1 started outside torch.distributed.run re-launches itself as a CHILD
 `python -m torch.distributed.run --nproc-per-node N ... bench.py ...` (before any
@@ -23,16 +34,18 @@ build (sdp_build_info() != 0: kernel-skip or stamp code compiled in) and a
 non-zero kernel-skip mask, and records every SDPNET_* environment variable
 (`config.knobs`, empty in a default run) and the loaded library's md5.
 
-Also reported on the same JSON line:
+With --full, also reported on the same JSON line (each takes GPU or CPU runs of its own
+after the headline's timed region):
   roofline     — dominant kernel (the bf16 fast GEMM, ~98 % of FLOPs): algorithmic
                  FLOPs per step / the union of its launch intervals in a replay of
                  the timed schedule, vs the dense bf16 MFMA peak.
-  secondary    — (N=1, default on) the other single-GPU BASELINE configs timed in the
+  secondary    — (N=1, --no-secondary skips it) the other single-GPU BASELINE configs timed in the
                  same process after the headline: configs[2] XL bs512 forward and
                  configs[4]'s per-GPU XL training step (bs 120).
   cpu_baseline — the oracle (the reference's math in stock PyTorch CPU ops,
                  oracle/sdpnet_oracle.py) on this host's cores, bounded samples of
-                 M bs16, configs[0] XXS bs4 and XL bs16, rank 0 at N=1 only.
+                 M bs16, configs[0] XXS bs4 and XL bs16, rank 0 at N=1 only
+                 (--no-cpu-baseline skips it).
 """
 import argparse
 import json
@@ -267,7 +280,24 @@ def _progress(rank, msg):
         print(f"[bench] {time.strftime('%H:%M:%S')} {msg}", file=sys.stderr, flush=True)
 
 
-def train_step_bench(C, B, steps, warmup, dev, world, rank, local, global_batch):
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # array data; with the .npy headers the files stay under 64 MB
+
+
+def dump_outputs(path, arrays, world, rank):
+    """--dump-outputs: each tensor of `arrays` as float32 `path`/<name>.npy (<name>_rank<r> at N > 1).
+    Together they stay under DUMP_LIMIT_BYTES: an array above its share is cut to a fixed, seeded
+    sample of its elements (flattened, in index order), the same in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (4 * max(1, len(arrays)))
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a)
+
+
+def train_step_bench(C, B, steps, warmup, dev, world, rank, local, global_batch, dump=None):
     """BASELINE.json configs[4]: one training step = bf16-autocast forward + label-smoothed CE
     (training_tools.py:85-88) + backward (DDP bucketed gradient all-reduce over RCCL when
     N > 1, training_tools.py:36, :91) + GradScaler unscale / clip_grad_norm_(5) / AdamW
@@ -296,11 +326,11 @@ def train_step_bench(C, B, steps, warmup, dev, world, rank, local, global_batch)
             loss = sdpnet_train.cross_entropy(out, y, 0.1)
         opt.scale(loss).backward()              # GradScaler.scale on the device scale (no sync)
         opt.step(grad_scale=None, max_norm=5.0)  # unscale / inf check / clip / AdamW / scale update
-        return loss
+        return loss, out
 
     _progress(rank, f"{C['name']} training bs {B}: model built, {max(1, warmup)} warmup steps")
     for _ in range(max(1, warmup)):
-        loss = step()
+        loss, logits = step()
     torch.cuda.synchronize()
     _progress(rank, "warmup done")
     if world > 1:
@@ -309,7 +339,7 @@ def train_step_bench(C, B, steps, warmup, dev, world, rank, local, global_batch)
     taken0 = float(opt._steps[0])
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss = step()
+        loss, logits = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -319,6 +349,8 @@ def train_step_bench(C, B, steps, warmup, dev, world, rank, local, global_batch)
     # GradScaler skips (inf/nan grads) did no optimizer work: count them, none expected
     skipped = int(steps - (float(opt._steps[0]) - taken0))
     assert skipped == 0, f"{skipped} optimizer steps skipped by the GradScaler inside the timed region"
+    if dump:
+        dump_outputs(dump, {"logits": logits, "loss": loss}, world, rank)
     gf = 3 * flops_per_image(cfg) / 1e9   # forward + dX + dW GEMMs (3x forward)
     value = total / el
     out = {
@@ -333,7 +365,7 @@ def train_step_bench(C, B, steps, warmup, dev, world, rank, local, global_batch)
         "skipped_steps": skipped, "grad_scale": float(opt.scaler[0]),
         "loss": round(float(loss.detach()), 4), "peak_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1),
     }
-    del m, net, opt, x, y
+    del m, net, opt, x, y, logits
     return out
 
 
@@ -347,7 +379,8 @@ def train_bench(args, C, world, rank, local):
         dist.init_process_group("nccl", device_id=dev)
     rec = library_record()
     lo, hi = sharding.shard_bounds(args.batch * world, world, rank)
-    out = train_step_bench(C, hi - lo, args.steps, args.warmup, dev, world, rank, local, args.batch * world)
+    out = train_step_bench(C, hi - lo, args.steps, args.warmup, dev, world, rank, local, args.batch * world,
+                           dump=args.dump_outputs)
     out["config"].update(rec)
     if rank == 0:
         print(json.dumps(out), flush=True)
@@ -356,7 +389,8 @@ def train_bench(args, C, world, rank, local):
         dist.destroy_process_group()
 
 
-def forward_bench(C, B, steps, warmup, dev, world, rank, streams=0, graph=True, roofline=True, config="m"):
+def forward_bench(C, B, steps, warmup, dev, world, rank, streams=0, graph=True, roofline=True, config="m",
+                  keep_cpu_sd=True, dump=None):
     """One config's eval forward: an fp32 batch resident in HBM under torch.autocast("cuda", bf16)
     (the reference's bf16 forward, training_tools.py:85; the patch kernel reads the fp32 image),
     W warmup forwards, a HIP graph of one forward (both sub-batch streams), K timed replays
@@ -371,7 +405,7 @@ def forward_bench(C, B, steps, warmup, dev, world, rank, streams=0, graph=True, 
     m = sdp.MainModel.from_dict(**cfg).eval()
     if streams > 0:
         m.num_streams = streams
-    cpu_sd = {k: v.detach().clone() for k, v in m.state_dict().items()} if rank == 0 and world == 1 else None
+    cpu_sd = {k: v.detach().clone() for k, v in m.state_dict().items()} if keep_cpu_sd and rank == 0 and world == 1 else None
     m = m.to(dev)
     g = torch.Generator(device="cpu").manual_seed(1000 + rank)
     x = torch.randn(B, 3, 224, 224, generator=g).to(dev)   # fp32, resident in HBM
@@ -404,12 +438,14 @@ def forward_bench(C, B, steps, warmup, dev, world, rank, streams=0, graph=True, 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        run()
+        r = run()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     el = sharding.max_over_ranks(time.perf_counter() - t0, device=dev)
     total_imgs = int(sharding.sum_over_ranks(B * steps, device=dev))
+    if pgraph is None:
+        y = r   # eager: the last timed step's own result (a replay writes into y)
     assert y.dtype == torch.bfloat16 and torch.isfinite(y.float()).all()
     value = total_imgs / el
     ms_step = 1e3 * el / steps
@@ -428,10 +464,12 @@ def forward_bench(C, B, steps, warmup, dev, world, rank, streams=0, graph=True, 
         "model_mfma_frac": round(value * gf * 1e9 / (world * MFMA_BF16_PEAK_TFLOPS * 1e12), 4),
     }
     _progress(rank, f"{steps} timed forwards: {value:.1f} img/s")
+    if dump:
+        dump_outputs(dump, {"logits": y}, world, rank)
     if roofline:
         out["roofline"] = gemm_roofline(step, dev, ms_step, config)
         _progress(rank, "roofline replays done")
-    del pgraph, m, x, y
+    del pgraph, m, x, y, r
     return out, cpu_sd
 
 
@@ -546,10 +584,14 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="m",
                     help="m = the BASELINE metric's workload (default); xl = configs[2]; xl_train = configs[4]")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (0 = the config's: M 256, XL 512)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as float32 DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the GEMM roofline, the secondary configs and the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the XL forward / XL training lines timed after the headline at N=1")
+                    help="with --full: skip the XL forward / XL training lines timed after the headline at N=1")
     ap.add_argument("--secondary-steps", type=int, default=20)
     ap.add_argument("--prof-steps", type=int, default=1, help="forwards per profiled graph replay (roofline)")
     ap.add_argument("--streams", type=int, default=0, help="sub-batch streams per GPU (0 = model default)")
@@ -559,6 +601,8 @@ def main():
     cfg = C["cfg"]
     if args.batch <= 0:
         args.batch = C["batch"]
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -594,7 +638,8 @@ def main():
     # contiguous shard (images are independent, no collective on the data path)
     lo, hi = sharding.shard_bounds(args.batch * world, world, rank)
     out, cpu_sd = forward_bench(C, hi - lo, args.steps, args.warmup, dev, world, rank, streams=args.streams,
-                                graph=not args.no_graph, roofline=True, config=args.config)
+                                graph=not args.no_graph, roofline=args.full, config=args.config,
+                                keep_cpu_sd=args.full and not args.no_cpu_baseline, dump=args.dump_outputs)
     out["config"].update({"global_batch": args.batch * world,
                           "parallelism": f"dp{world} independent batch shards (no collective)",
                           "comm_world": comm_world, "comm_backend": "nccl (RCCL)" if world > 1 else None,
@@ -603,7 +648,7 @@ def main():
     cpu_sds = {}
     if cpu_sd is not None:
         cpu_sds[C["name"]] = (cpu_sd, cfg)
-    if world == 1 and not args.no_secondary and args.config == "m":
+    if args.full and world == 1 and not args.no_secondary and args.config == "m":
         # configs[2] and configs[4] under the same clock, after the headline's timed region
         sec = {}
         ks = max(1, min(args.secondary_steps, args.steps))
@@ -623,7 +668,7 @@ def main():
         sec["xl_train"]["per_gpu_batch"] = CONFIGS["xl_train"]["batch"]
         out["secondary"] = sec
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_sds:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and cpu_sds:
         if args.config == "m":
             torch.manual_seed(231424314)
             import model as sdp

@@ -18,8 +18,8 @@ for s in "$@"; do
     model) step model 1200 python -m pytest tests/test_gpu_model.py -q -p no:cacheprovider -rf ;;
     all) step all 1500 python -u -m pytest tests/ -m gpu -q -p no:cacheprovider -rf --timeout 240 --timeout-method thread ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench 600 python bench.py --steps 10 --warmup 3 ;;
-    benchq) step benchq 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline ;;
+    bench) step bench 600 python bench.py --full --steps 10 --warmup 3 ;;
+    benchq) step benchq 600 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline ;;
     streams) step s1 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --streams 1 &&
              step s2 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --streams 2 &&
              step s3 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --streams 3 &&
@@ -37,7 +37,7 @@ for s in "$@"; do
          step gpmcC 600 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/gpmcC -o run --output-format csv -- $GB &&
          step gpmcD 600 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum -d gpurun_out/gpmcD -o run --output-format csv -- $GB ;;
     prof) export TMPDIR=/tmp; rm -rf gpurun_out/prof gpurun_out/pmcF gpurun_out/pmcW
-          BP="python bench.py --steps 3 --warmup 1 --no-graph --streams 1 --no-cpu-baseline --prof-steps 1"
+          BP="python bench.py --full --steps 3 --warmup 1 --no-graph --streams 1 --no-cpu-baseline --prof-steps 1"
           step prof 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- $BP &&
           step pmcF 900 rocprofv3 --pmc FETCH_SIZE -d gpurun_out/pmcF -o run --output-format csv -- $BP &&
           step pmcW 900 rocprofv3 --pmc WRITE_SIZE -d gpurun_out/pmcW -o run --output-format csv -- $BP ;;

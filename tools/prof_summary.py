@@ -3,8 +3,9 @@
   python tools/prof_summary.py --round r01 --prof gpurun_out/prof --fetch gpurun_out/pmcF \
       --write gpurun_out/pmcW --bench-log gpurun_out/prof.log
 
-Inputs (all from the same command, `bench.py --steps 3 --warmup 1 --no-graph --streams 1
---no-cpu-baseline --prof-steps 1`, so every pass runs the same launch mix):
+Inputs (all from the same command, `bench.py --full --steps 3 --warmup 1 --no-graph --streams 1
+--no-cpu-baseline --prof-steps 1`, so every pass runs the same launch mix; --full because the
+summary quotes the line's roofline):
   --prof   rocprofv3 --kernel-trace --stats directory (run_kernel_stats.csv, run_kernel_trace.csv)
   --fetch  rocprofv3 --pmc FETCH_SIZE directory   (own pass; FETCH_SIZE costs 3 TCC slots)
   --write  rocprofv3 --pmc WRITE_SIZE directory   (own pass)
@@ -74,8 +75,8 @@ def main():
     ap.add_argument("--write")
     ap.add_argument("--bench-log")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles"))
-    ap.add_argument("--cmd", default="bench.py --steps 3 --warmup 1 --no-graph --streams 1 --no-cpu-baseline "
-                                     "--prof-steps 1", help="the profiled bench.py arguments (for the summary text)")
+    ap.add_argument("--cmd", default="bench.py --full --steps 3 --warmup 1 --no-graph --streams 1 "
+                                     "--no-cpu-baseline --prof-steps 1", help="the profiled bench.py arguments (for the summary text)")
     ap.add_argument("--graph", action="store_true", help="the profiled command replays the 2-stream HIP graph")
     ap.add_argument("--config", default="m", help="bench.py --config of the profiled command (m, xl)")
     args = ap.parse_args()
