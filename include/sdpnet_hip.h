@@ -20,13 +20,34 @@
  *     (grp = P, gstride = R+P, off = R) without gather/scatter copies.
  *   - Activation codes: 0 none, 1 gelu, 2 relu, 3 tanh, 4 sigmoid,
  *     5 leaky_relu (0.01), 6 selu, 7 kelu (model.py:13-24,
- *     training_utilities.py:91-92).  GELU is the erf form x * Phi(x) everywhere except
- *     the bf16 fast-GEMM epilogue (Phi through erfc by Abramowitz & Stegun 7.1.26: |diff|
- *     <= 4.2e-7 against double-precision erf, below the 4.5e-7 of the fp32 formula with
- *     erff), which uses the tanh form which uses the tanh form
- *     x * sigmoid(sqrt(2/pi) (x + 0.044715 x^3)) (|diff| <= 4.7e-4, about one bf16
- *     rounding of the output; a DECLARED deviation from nn.GELU(), model.py:15) unless
- *     sdp_gemm_set_exact_gelu(1) is set.
+ *     training_utilities.py:91-92).  GELU is the erf form x * Phi(x) (Phi through erfc by
+ *     Abramowitz & Stegun 7.1.26: |diff| <= 4.2e-7 against double-precision erf, below the
+ *     4.5e-7 of the fp32 formula with erff) everywhere except the bf16 fast-GEMM epilogue,
+ *     which uses the tanh form x * sigmoid(2 sqrt(2/pi) (x + 0.044715 x^3))
+ *     = 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))) (|diff| <= 4.7e-4, about one bf16
+ *     rounding of the output; a DECLARED deviation from nn.GELU(), model.py:15) on every tile
+ *     of both fast kernels, unless sdp_gemm_set_exact_gelu(1) is set.
+ *   - bf16 rounding points.  bf16 kernels take bf16 operands, compute in fp32 and round to
+ *     bf16 (to nearest even) at these points and no others (tests/test_gpu_bf16_budget.py
+ *     holds each kernel to the fp64 result rounded exactly there):
+ *       fast GEMM 9:   the output, once: bf16(act(acc + b [+ R]) [+ R]).
+ *       fast GEMM 14:  the whole-line epilogue stages bf16(act(acc + b)) and adds the residual
+ *                      to that staged value: bf16(bf16(act(acc + b)) + R), also for resid_pre
+ *                      without an activation (resid_pre with one runs kernel 9's epilogue).
+ *                      Without a residual: once.  The LN fold is fp32 before the activation.
+ *       sdp_gemm_train_epi: mode 1 Y = bf16(acc + b), Y2 = bf16(dropout(act(Y))) of the
+ *                      stored Y; mode 2 Y = bf16(dropout(bf16(acc)) * act'(Z)).
+ *       sdp_fold_ln_weight: Wf = bf16(W * gamma); colsum sums the rounded Wf.
+ *       flash attention (every bf16 tier): the head-normalised q and k; P = exp(s - running
+ *                      max) for the P V product only (the row sum takes the unrounded P); the
+ *                      output.  Scores, scale and softmax statistics are fp32.
+ *       MFMA depthwise conv (tier 3): the LayerNorm'd input, the fp32 *weights* (to bf16,
+ *                      once per launch), the output: bf16(bf16(LN(x)) (*) bf16(w) + bias).
+ *                      Tiers 1 and 2 multiply by the fp32 weights.
+ *       flash training attention: forward dropout(P) (un-normalised) for P V, and O; backward
+ *                      dropout(P) (normalised by the saved LSE) for dV, dS = P o (dP - D) for dQ
+ *                      and dK, with D = rowsum(dO o O) of the stored bf16 O; the outputs dQ,
+ *                      dK, dV.  LSE and D are fp32.
  */
 #ifndef SDPNET_HIP_H
 #define SDPNET_HIP_H

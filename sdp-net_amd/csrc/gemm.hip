@@ -71,8 +71,9 @@ struct Epi {
 // fold: v = r * acc + (b - r * mu * s) for one element (generic paths)
 SDP_DEV float ln_fold(float acc, float r, float rmu, float s, float b) { return fmaf(r, acc, fmaf(-rmu, s, b)); }
 
-// Apply the epilogue to 4 consecutive columns n..n+3 of logical row m.
-template <typename T>
+// Apply the epilogue to 4 consecutive columns n..n+3 of logical row m.  FAST_GELU: GELU in the
+// fast kernel's tanh form (its ragged tiles; the generic kernel keeps the erf form).
+template <typename T, bool FAST_GELU = false>
 SDP_DEV void epi_store4(const Epi<T>& e, int64_t m, int n, int N, f32x4 acc) {
   float v[4] = {acc[0], acc[1], acc[2], acc[3]};
   const bool full = (n + 3 < N);
@@ -109,7 +110,7 @@ SDP_DEV void epi_store4(const Epi<T>& e, int64_t m, int n, int N, f32x4 acc) {
   }
   if (e.act != ACT_NONE) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) v[r] = apply_act(e.act, v[r]);
+    for (int r = 0; r < 4; ++r) v[r] = FAST_GELU ? gelu_fast(v[r]) : apply_act(e.act, v[r]);
   }
   if (e.resid && !e.resid_pre) {
 #pragma unroll
@@ -165,6 +166,8 @@ SDP_DEV void tile_epilogue(const Epi<bf16_t>& epi, f32x4 (&acc)[4][8], int m0, i
   // D[n][m]: lane holds n = base + 4*fq + r, m = base + fr.
   const bool full_n = (n0 + BN <= N);
   if (!full_n) {
+    // the same activation form as the full tiles: a column's result must not depend on where
+    // the tile boundaries fall (epi_store4's own GELU is the generic kernel's erf form)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int m = m0 + wm * 128 + j * 16 + fr;
@@ -172,7 +175,7 @@ SDP_DEV void tile_epilogue(const Epi<bf16_t>& epi, f32x4 (&acc)[4][8], int m0, i
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int n = n0 + wn * 64 + i * 16 + fq * 4;
-        if (n < N) epi_store4<bf16_t>(epi, m, n, N, acc[i][j]);
+        if (n < N) epi_store4<bf16_t, ACT == ACT_GELU>(epi, m, n, N, acc[i][j]);
       }
     }
     return;
