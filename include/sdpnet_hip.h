@@ -533,6 +533,29 @@ int sdp_ce_loss_counted(int dtype, const void* logits, int64_t ldl, const int64_
 int sdp_ce_loss_soft(int dtype, const void* logits, int64_t ldl, const float* targets, int64_t ldt, int B, int K,
                      float eps, float grad_scale, void* dlogits, int64_t ldd, float* loss, void* stream);
 
+/* Label-smoothed binary cross entropy with logits, mean over all B * K elements (the reference's
+ * BCEWithLogitsLoss(num_classes = K, label_smoothing), training_utilities.py:95-107, selected by
+ * use_cross_entropy = False at training_tools.py:74): t' = (1 - eps) t + eps / K, t the one-hot
+ * of the label (sdp_bce_loss) or the fp32 target row [B][ldt] (sdp_bce_loss_soft);
+ * *loss += 1 / (B K) * sum bce(x, t') (fp32, one atomic per row), bce(x, t) = (1 - t) x + m +
+ * log(exp(-m) + exp(-x - m)), m = max(-x, 0) (ATen's form, as sdp_logits_metrics);
+ * dlogits = grad_scale / (B K) * (sigmoid(x) - t') (may be NULL).  fp32 or bf16 logits.  A hard
+ * label outside [0, K) makes its row's loss and gradient NaN and is never dereferenced. */
+int sdp_bce_loss(int dtype, const void* logits, int64_t ldl, const int64_t* labels, int B, int K, float eps,
+                 float grad_scale, void* dlogits, int64_t ldd, float* loss, void* stream);
+int sdp_bce_loss_soft(int dtype, const void* logits, int64_t ldl, const float* targets, int64_t ldt, int B, int K,
+                      float eps, float grad_scale, void* dlogits, int64_t ldd, float* loss, void* stream);
+
+/* Multi-tensor weight average (EMA_model.update_parameters, training_tools.py:291-297) over the
+ * block table of sdp_adamw: out[t][i] = fl(fl(d * a[t][i]) + fl(c * b[t][i])), three fp32
+ * roundings and no FMA, so the result is bit-identical to torch's `d * e + c * w`.  A running
+ * average passes a = out = the average and b = the weights; the reference's update (which first
+ * overwrites the average with the weights, training_tools.py:295-296) passes a = b = the weights.
+ * Tensors are fp32 and contiguous; 16-byte accesses where a tensor's three addresses are 16-byte
+ * aligned, element accesses otherwise.  nblocks == 0 is a no-op. */
+int sdp_ema_update(float* const* out, float* const* a, float* const* b, const int64_t* sizes, const void* blocks,
+                   int nblocks, float d, float c, void* stream);
+
 /* Multi-tensor optimizer step over fp32 tensors (device arrays of pointers / sizes and a
  * block table of sdp_mt_block_bytes()-sized {int tensor; int64 start} entries, 4096
  * elements per block):

@@ -23,6 +23,8 @@
 //  * ce_loss — label-smoothed cross entropy (training_tools.py:76) loss and dlogits.
 //  * sumsq / adamw — fused gradient norm (clip_grad_norm_, unscale, inf check) and the
 //    multi-tensor AdamW update (torch.optim.AdamW semantics), no host synchronisation.
+//  * bce_loss — label-smoothed BCE-with-logits (training_utilities.py:95-107) loss and dlogits.
+//  * ema_update — multi-tensor weight average of EMA_model (training_tools.py:291-297).
 #include "common.h"
 
 static RowMap mk_tmap(int grp, int64_t gstride, int off) {
@@ -2256,6 +2258,89 @@ extern "C" int sdp_ce_loss_soft(int dtype, const void* logits, int64_t ldl, cons
 }
 
 // ---------------------------------------------------------------------------
+// Label-smoothed binary cross entropy with logits, mean over all B * K elements (the
+// BCEWithLogitsLoss of training_utilities.py:95-107, use_cross_entropy: False at
+// training_tools.py:74): t' = (1 - eps) t + eps / K with t the one-hot of the label or the
+// fp32 target row,
+//   loss    += 1 / (B K) * sum_k bce(x_k, t'_k),  bce(x, t) = (1 - t) x + m + log(exp(-m) + exp(-x - m)),
+//              m = max(-x, 0) (ATen's form, as metrics_k in eval.hip)
+//   dlogits  = grad_scale / (B K) * (sigmoid(x) - t')
+// One wave per row, one atomic per row, as ce_k.  A hard label outside [0, K) is only ever
+// compared with the column index: its row's loss and gradient are NaN.
+// ---------------------------------------------------------------------------
+template <typename T, bool SOFT>
+__global__ __launch_bounds__(256) void bce_k(const T* __restrict__ L, int64_t ldl, const int64_t* __restrict__ y,
+                                             const float* __restrict__ tg, int64_t ldt, int B, int K, float eps,
+                                             float grad_scale, T* __restrict__ D, int64_t ldd,
+                                             float* __restrict__ loss) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= B) return;
+  const T* lp = L + r * ldl;
+  const float* tp = SOFT ? tg + r * ldt : nullptr;
+  int64_t lab = 0;
+  float bad = 0.0f;
+  if constexpr (!SOFT) {
+    lab = y[r];
+    if (!(lab >= 0 && lab < K)) bad = NAN;
+  }
+  const float on = 1.0f - eps, off = eps / (float)K;
+  const float inv_n = 1.0f / ((float)B * (float)K);
+  float s = 0.f;
+  for (int c = lane; c < K; c += 64) {
+    const float x = to_f<T>(lp[c]);
+    float t;
+    if constexpr (SOFT) t = fmaf(on, tp[c], off);
+    else t = (c == lab ? on : 0.0f) + off;
+    const float m = fmaxf(-x, 0.f);
+    s += (1.0f - t) * x + m + logf(expf(-m) + expf(-x - m));
+  }
+  s = wave_sum(s);
+  if (lane == 0) atomicAdd(loss, s * inv_n + bad);
+  if (!D) return;
+  const float sc = grad_scale * inv_n;
+  for (int c = lane; c < K; c += 64) {
+    const float x = to_f<T>(lp[c]);
+    float t;
+    if constexpr (SOFT) t = fmaf(on, tp[c], off);
+    else t = (c == lab ? on : 0.0f) + off;
+    const float sg = 1.0f / (1.0f + expf(-x));
+    D[r * ldd + c] = from_f<T>(sc * (sg - t) + bad);
+  }
+}
+
+template <bool SOFT>
+static int bce_launch(int dtype, const void* logits, int64_t ldl, const int64_t* labels, const float* targets,
+                      int64_t ldt, int B, int K, float eps, float grad_scale, void* dlogits, int64_t ldd, float* loss,
+                      void* stream) {
+  if (!logits || !loss || B < 0 || K <= 0) return (int)hipErrorInvalidValue;
+  if (SOFT ? !targets : !labels) return (int)hipErrorInvalidValue;
+  if (B == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((B + 3) / 4);
+  if (dtype == 1)
+    hipLaunchKernelGGL((bce_k<bf16_t, SOFT>), grid, dim3(256), 0, s, (const bf16_t*)logits, ldl, labels, targets, ldt,
+                       B, K, eps, grad_scale, (bf16_t*)dlogits, ldd, loss);
+  else if (dtype == 0)
+    hipLaunchKernelGGL((bce_k<float, SOFT>), grid, dim3(256), 0, s, (const float*)logits, ldl, labels, targets, ldt, B,
+                       K, eps, grad_scale, (float*)dlogits, ldd, loss);
+  else
+    return (int)hipErrorInvalidValue;
+  return SDP_CHECK_LAUNCH();
+}
+
+extern "C" int sdp_bce_loss(int dtype, const void* logits, int64_t ldl, const int64_t* labels, int B, int K, float eps,
+                            float grad_scale, void* dlogits, int64_t ldd, float* loss, void* stream) {
+  return bce_launch<false>(dtype, logits, ldl, labels, nullptr, 0, B, K, eps, grad_scale, dlogits, ldd, loss, stream);
+}
+
+extern "C" int sdp_bce_loss_soft(int dtype, const void* logits, int64_t ldl, const float* targets, int64_t ldt, int B,
+                                 int K, float eps, float grad_scale, void* dlogits, int64_t ldd, float* loss,
+                                 void* stream) {
+  return bce_launch<true>(dtype, logits, ldl, nullptr, targets, ldt, B, K, eps, grad_scale, dlogits, ldd, loss, stream);
+}
+
+// ---------------------------------------------------------------------------
 // Multi-tensor gradient norm and AdamW.  Tensors are fp32; the work list is a table of
 // (tensor, first element) per 4096-element block built once by the host.
 //   sdp_grad_sumsq: state[0] += sum g^2 over every tensor, state[1] = 1 if any g is non-finite
@@ -2467,6 +2552,55 @@ extern "C" int sdp_adamw_finish(float* state, float* scale_tracker, float growth
     return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(adamw_finish_k, dim3(1), dim3(256), 0, (hipStream_t)stream, state, scale_tracker, growth,
                      backoff, interval, steps, nsteps);
+  return SDP_CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------------------
+// Multi-tensor weight average (EMA_model.update_parameters, training_tools.py:291-297) over the
+// block table of sdp_adamw: out[t][i] = fl(fl(d * a[t][i]) + fl(c * b[t][i])), every operation
+// rounded to fp32 on its own, which is what torch's `d * e + c * w` computes as three
+// elementwise ops -- bit for bit.  The HIP headers define __fmul_rn / __fadd_rn as plain `*` and
+// `+` that the compiler may contract into an FMA, so the expression is written out with
+// contraction switched off.  a == out (the running average) or a == b (the reference's
+// overwrite-then-mix) are both fine: every element is read before it is written, by one thread.
+// ---------------------------------------------------------------------------
+SDP_DEV float ema_mix(float d, float a, float c, float b) {
+#pragma clang fp contract(off)
+  const float da = d * a;
+  const float cb = c * b;
+  return da + cb;
+}
+
+__global__ __launch_bounds__(256) void ema_k(float* const* __restrict__ outs, float* const* __restrict__ as,
+                                             float* const* __restrict__ bs, const int64_t* __restrict__ sizes,
+                                             const MTBlock* __restrict__ blocks, float d, float c) {
+  const MTBlock bl = blocks[blockIdx.x];
+  float* o = outs[bl.tensor];
+  const float* a = as[bl.tensor];
+  const float* b = bs[bl.tensor];
+  const int64_t n = sizes[bl.tensor];
+  const int64_t end = min(n, bl.start + 4096);
+  int64_t i0 = bl.start;
+  // block starts are multiples of 4096 elements, so the tensor's base alignment is the block's
+  if ((((uintptr_t)o | (uintptr_t)a | (uintptr_t)b) & 15) == 0) {
+    const int nv = (int)((end - i0) >> 2);  // <= 1024 16-B groups: 4 per thread
+    for (int v = threadIdx.x; v < nv; v += 256) {
+      const f32x4 x = *(const f32x4*)(a + i0 + 4 * v);
+      const f32x4 y = *(const f32x4*)(b + i0 + 4 * v);
+      *(f32x4*)(o + i0 + 4 * v) =
+          f32x4{ema_mix(d, x[0], c, y[0]), ema_mix(d, x[1], c, y[1]), ema_mix(d, x[2], c, y[2]), ema_mix(d, x[3], c, y[3])};
+    }
+    i0 += 4 * (int64_t)nv;
+  }
+  for (int64_t i = i0 + threadIdx.x; i < end; i += 256) o[i] = ema_mix(d, a[i], c, b[i]);
+}
+
+extern "C" int sdp_ema_update(float* const* out, float* const* a, float* const* b, const int64_t* sizes,
+                              const void* blocks, int nblocks, float d, float c, void* stream) {
+  if (!out || !a || !b || !sizes || !blocks || nblocks < 0) return (int)hipErrorInvalidValue;
+  if (nblocks == 0) return 0;
+  hipLaunchKernelGGL(ema_k, dim3(nblocks), dim3(256), 0, (hipStream_t)stream, out, a, b, sizes,
+                     (const MTBlock*)blocks, d, c);
   return SDP_CHECK_LAUNCH();
 }
 

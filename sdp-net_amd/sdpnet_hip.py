@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import struct
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -123,6 +124,9 @@ _SIGS = {
     "sdp_ce_count": ([_vp, _i32, _i64, _vp, _vp], _i32),
     "sdp_ce_loss_counted": ([_i32, _vp, _i64, _vp, _i32, _i32, _f32, _f32, _i64, _vp, _vp, _i64, _vp, _vp], _i32),
     "sdp_ce_loss_soft": ([_i32, _vp, _i64, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _i64, _vp, _vp], _i32),
+    "sdp_bce_loss": ([_i32, _vp, _i64, _vp, _i32, _i32, _f32, _f32, _vp, _i64, _vp, _vp], _i32),
+    "sdp_bce_loss_soft": ([_i32, _vp, _i64, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _i64, _vp, _vp], _i32),
+    "sdp_ema_update": ([_vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp], _i32),
     "sdp_mt_block_bytes": ([], _i32),
     "sdp_grad_sumsq": ([_vp, _vp, _vp, _i32, _vp, _vp], _i32),
     "sdp_adamw": ([_vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _vp], _i32),
@@ -965,6 +969,66 @@ def ce_loss_soft(logits: torch.Tensor, targets: torch.Tensor, eps: float, grad_s
                                 targets.stride(0), B, K, float(eps), float(grad_scale), _ptr(dlogits),
                                 dlogits.stride(0) if dlogits is not None else 0, loss.data_ptr(), _stream(loss))
     _check(rc, "ce_loss_soft")
+
+
+def bce_loss(logits: torch.Tensor, labels: torch.Tensor, eps: float, grad_scale: float,
+             dlogits: Optional[torch.Tensor], loss: torch.Tensor):
+    """Label-smoothed BCE with logits on int64 class labels, mean over all B * K elements
+    (training_utilities.py:95-107); loss is accumulated into ``loss`` (fp32, 1 element)."""
+    _need_cuda(logits, labels, dlogits, loss)
+    _req(labels.dtype == torch.int64 and loss.dtype == torch.float32, "bce_loss dtypes")
+    _req(logits.dim() == 2 and logits.stride(1) == 1, "bce_loss: row-major [B, K] logits")
+    B, K = logits.shape
+    _req(labels.numel() == B, "bce_loss: one label per row")
+    _req(dlogits is None or (dlogits.shape == logits.shape and dlogits.dtype == logits.dtype
+                             and dlogits.stride(1) == 1), "bce_loss: dlogits like logits")
+    labels = labels.contiguous()
+    rc = lib().sdp_bce_loss(dcode(logits.dtype), logits.data_ptr(), logits.stride(0), labels.data_ptr(), B, K,
+                            float(eps), float(grad_scale), _ptr(dlogits),
+                            dlogits.stride(0) if dlogits is not None else 0, loss.data_ptr(), _stream(loss))
+    _check(rc, "bce_loss")
+
+
+def bce_loss_soft(logits: torch.Tensor, targets: torch.Tensor, eps: float, grad_scale: float,
+                  dlogits: Optional[torch.Tensor], loss: torch.Tensor):
+    """The same loss on fp32 target rows [B, K] (the CutMix / MixUp targets)."""
+    _need_cuda(logits, targets, dlogits, loss)
+    _req(logits.dim() == 2 and logits.stride(1) == 1, "bce_loss_soft: row-major [B, K] logits")
+    _req(targets.dtype == torch.float32 and loss.dtype == torch.float32 and targets.shape == logits.shape
+         and targets.stride(1) == 1, "bce_loss_soft: fp32 [B, K] targets")
+    _req(dlogits is None or (dlogits.shape == logits.shape and dlogits.dtype == logits.dtype
+                             and dlogits.stride(1) == 1), "bce_loss_soft: dlogits like logits")
+    B, K = logits.shape
+    rc = lib().sdp_bce_loss_soft(dcode(logits.dtype), logits.data_ptr(), logits.stride(0), targets.data_ptr(),
+                                 targets.stride(0), B, K, float(eps), float(grad_scale), _ptr(dlogits),
+                                 dlogits.stride(0) if dlogits is not None else 0, loss.data_ptr(), _stream(loss))
+    _check(rc, "bce_loss_soft")
+
+
+def mt_block_table(numels, dev: torch.device) -> Tuple[torch.Tensor, int]:
+    """The work list of the multi-tensor kernels for tensors of ``numels`` elements: one
+    sdp_mt_block_bytes()-sized {int tensor; int64 start} entry per 4096 elements, on ``dev``."""
+    bb = lib().sdp_mt_block_bytes()
+    blocks = [(t, s0) for t, n in enumerate(numels) for s0 in range(0, n, 4096)]
+    raw = bytearray(bb * len(blocks))
+    for i, (t, s0) in enumerate(blocks):
+        struct.pack_into("<iiq", raw, i * bb, t, 0, s0)
+    tab = (torch.frombuffer(raw, dtype=torch.uint8).to(dev) if blocks
+           else torch.empty(0, dtype=torch.uint8, device=dev))
+    return tab, len(blocks)
+
+
+def ema_update(out_ptrs: torch.Tensor, a_ptrs: torch.Tensor, b_ptrs: torch.Tensor, sizes: torch.Tensor,
+               blocks: torch.Tensor, nblocks: int, d: float, c: float):
+    """out[t] = d * a[t] + c * b[t] (each operation rounded to fp32) for every tensor of the
+    device address tables, one launch (``blocks`` from mt_block_table)."""
+    _need_cuda(out_ptrs, a_ptrs, b_ptrs, sizes, blocks)
+    _req(out_ptrs.dtype == a_ptrs.dtype == b_ptrs.dtype == sizes.dtype == torch.int64, "ema_update: int64 tables")
+    _req(out_ptrs.numel() == a_ptrs.numel() == b_ptrs.numel() == sizes.numel(), "ema_update: one entry per tensor")
+    _req(blocks.numel() == nblocks * lib().sdp_mt_block_bytes(), "ema_update: block table size")
+    rc = lib().sdp_ema_update(out_ptrs.data_ptr(), a_ptrs.data_ptr(), b_ptrs.data_ptr(), sizes.data_ptr(),
+                              blocks.data_ptr(), int(nblocks), float(d), float(c), _stream(sizes))
+    _check(rc, "ema_update")
 
 
 def transpose(x: torch.Tensor) -> torch.Tensor:

@@ -18,9 +18,11 @@ libsdpnet_hip.so:
             depthwise conv: input grad = conv with the flipped kernel, weight grad = dw_wgrad |
             attention: dV = Pd^T dO, dPd = dO V^T, dS = softmax', dQ = dS K, dK = dS^T Q |
             q/k head-LN backward
-  loss      cross_entropy(): label-smoothed CE + dlogits in one kernel (training_tools.py:76, :88)
+  loss      cross_entropy(): label-smoothed CE + dlogits in one kernel (training_tools.py:76, :88);
+            bce_with_logits(): the BCE loss of use_cross_entropy: False (:74) the same way
   optimizer AdamW: one multi-tensor kernel for GradScaler unscale + inf check +
             clip_grad_norm_ + AdamW (training_tools.py:91-99, :235), no host sync.
+  average   EMA: the weight average of EMA_model (training_tools.py:282-302), one multi-tensor kernel.
 
 Randomness: dropout masks (layers.py:291, :301-308, head :450-454) come from a counter
 hash of a per-op seed drawn from torch's CPU generator (so ``torch.manual_seed`` fixes a
@@ -1578,6 +1580,126 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, label_smoothing: f
     return _CEFn.apply(logits, labels, float(label_smoothing), int(ignore_index))
 
 
+class _BCEFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, eps):
+        loss = torch.zeros(1, dtype=torch.float32, device=logits.device)
+        logits = logits.contiguous()
+        d = torch.empty_like(logits)
+        if targets.is_floating_point():  # probability rows (CutMix / MixUp, dataset_generator.py:105-110)
+            sp.bce_loss_soft(logits, targets.float().contiguous(), eps, 1.0, d, loss)
+        else:
+            sp.bce_loss(logits, targets, eps, 1.0, d, loss)
+        ctx.save_for_backward(d)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (d,) = ctx.saved_tensors
+        out = torch.empty_like(d)
+        M, K = d.shape
+        sc = g.float().reshape(1).expand(M).contiguous()
+        sp.rowscale_add(_dense(d), _dense(out), M, K, scale=sc, sgrp=1)
+        return out, None, None
+
+
+def bce_with_logits(logits: torch.Tensor, targets: torch.Tensor, label_smoothing: float = 0.1,
+                    num_classes: Optional[int] = None) -> torch.Tensor:
+    """The reference's ``BCEWithLogitsLoss(num_classes, label_smoothing)(logits, targets)``
+    (training_utilities.py:95-107, the loss of ``use_cross_entropy: False``, training_tools.py:74)
+    as one HIP kernel that also writes dlogits: targets smoothed to (1 - ls) t + ls / K, ATen's
+    binary_cross_entropy_with_logits, mean over all B * K elements.  ``targets`` are int64 class
+    indices [B] or float rows [B, K].  A class index outside [0, K) gives a NaN loss (one_hot
+    raises).  ``num_classes``, when given, must be K."""
+    if logits.dim() != 2:
+        raise ValueError(f"bce_with_logits takes [B, K] logits, got {tuple(logits.shape)}")
+    K = logits.shape[1]
+    if num_classes is not None and int(num_classes) != K:
+        raise ValueError(f"bce_with_logits: logits have {K} classes, num_classes is {num_classes}")
+    if targets.is_floating_point():
+        if targets.shape != logits.shape:
+            raise ValueError(f"bce_with_logits: float targets {tuple(targets.shape)} for logits {tuple(logits.shape)}")
+    elif targets.dtype != torch.int64 or targets.dim() != 1:
+        raise ValueError("bce_with_logits: targets are int64 class indices [B] or float rows [B, K]")
+    return _BCEFn.apply(logits, targets, float(label_smoothing))
+
+
+class EMA:
+    """The weight average of the reference's ``EMA_model`` (training_tools.py:282-302) with every
+    fp32 entry of the state dict updated by ONE multi-tensor HIP launch (``sdp_ema_update``)
+    instead of a copy, two multiplies and an add per entry.
+
+    ``ema_weights`` is a clone of ``model.state_dict()``, keys as the model gives them (a DDP or
+    compiled model's ``module.`` / ``_orig_mod.`` prefixes included).  With
+    ``reference_quirks=True`` (default) ``update_parameters`` does what the reference does:
+    its condition ``"num_batches_tracked" or "running" in keys`` (:295) is always true, so every
+    entry is overwritten with the current value w and then mixed with itself -- the stored value
+    is fl(fl(d w) + fl(c w)), d = float(decay), c = float(1 - decay), within 1 ulp of w but not an
+    average -- and non-floating entries become float32.  With ``reference_quirks=False`` it is
+    the exponential average e <- d e + c w, and non-floating entries are copied with their dtype.
+    Either way the fp32 results are bit-identical to the same expression in torch ops.  The
+    device address tables are rebuilt whenever a tensor of the model or of the average moves."""
+
+    def __init__(self, model: nn.Module, decay: float = 0.999, reference_quirks: bool = True,
+                 ema_model_name: str = "ema_model.pt"):
+        self.ema_weights = {k: v.clone().detach() for k, v in model.state_dict().items()}
+        self.decay = decay
+        self.reference_quirks = bool(reference_quirks)
+        self.ema_model_name = ema_model_name
+        self._tab = None
+        self._sig = None
+
+    @staticmethod
+    def _fused(e: torch.Tensor, v: torch.Tensor) -> bool:
+        return (e.dtype == torch.float32 and v.dtype == torch.float32 and e.is_cuda and v.device == e.device
+                and e.is_contiguous() and v.is_contiguous() and e.shape == v.shape and e.numel() > 0)
+
+    def _build(self, pairs, sig):
+        dev = pairs[0][0].device
+
+        def ptrs(ts):
+            return torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=dev)
+        blocks, nblocks = sp.mt_block_table([e.numel() for e, _ in pairs], dev)
+        self._tab = dict(e=ptrs([e for e, _ in pairs]), w=ptrs([v for _, v in pairs]), blocks=blocks, nblocks=nblocks,
+                         sizes=torch.tensor([e.numel() for e, _ in pairs], dtype=torch.int64, device=dev))
+        self._sig = sig
+
+    @torch.no_grad()
+    def update_parameters(self, model: nn.Module) -> None:
+        d, c = self.decay, 1 - self.decay
+        pairs = []
+        for k, v in model.state_dict().items():
+            e = self.ema_weights[k]
+            v = v.detach()
+            if self._fused(e, v):
+                pairs.append((e, v))
+            elif self.reference_quirks or not e.is_floating_point():
+                if self.reference_quirks:  # training_tools.py:295-297, as written
+                    e.copy_(v)
+                    self.ema_weights[k] = d * e + c * v
+                else:
+                    e.copy_(v)
+            else:  # a floating entry the kernel does not take (other dtype / device / layout)
+                e.copy_(d * e + c * v)
+        if not pairs:
+            return
+        sig = tuple((e.data_ptr(), v.data_ptr(), e.numel()) for e, v in pairs)
+        if sig != self._sig:
+            self._build(pairs, sig)
+        t = self._tab
+        if self.reference_quirks:
+            sp.ema_update(t["e"], t["w"], t["w"], t["sizes"], t["blocks"], t["nblocks"], d, c)
+        else:
+            sp.ema_update(t["e"], t["e"], t["w"], t["sizes"], t["blocks"], t["nblocks"], d, c)
+
+    def state_dict(self):
+        return self.ema_weights
+
+    def save_ema_model(self):
+        weights = {k: v.cpu() for k, v in self.ema_weights.items()}
+        torch.save(weights, self.ema_model_name)
+
+
 # SDPNET_ADAMW_PTR_CACHE=0: upload the gradient address table every step with a blocking copy (A/B)
 _GRAD_PTR_CACHE = os.environ.get("SDPNET_ADAMW_PTR_CACHE", "1") != "0"
 
@@ -1644,7 +1766,6 @@ class AdamW(torch.optim.Optimizer):
         return sig
 
     def _build(self, dev):
-        bb = sp.lib().sdp_mt_block_bytes()
         self._tables = []
         groups = [[p for p in group["params"] if p.grad is not None] for group in self.param_groups]
         counts = []
@@ -1670,20 +1791,12 @@ class AdamW(torch.optim.Optimizer):
             for i, p in enumerate(ps):
                 self.state[p]["step"] = steps[i]
             base += len(ps)
-            blocks = []
-            for ti, p in enumerate(ps):
-                for s0 in range(0, p.numel(), 4096):
-                    blocks.append((ti, s0))
-            raw = bytearray(bb * len(blocks))
-            for i, (t, s0) in enumerate(blocks):
-                struct.pack_into("<iiq", raw, i * bb, t, 0, s0)
-            btab = (torch.frombuffer(raw, dtype=torch.uint8).to(dev) if blocks
-                    else torch.empty(0, dtype=torch.uint8, device=dev))
+            btab, nblocks = sp.mt_block_table([p.numel() for p in ps], dev)
             sizes = torch.tensor([p.numel() for p in ps], dtype=torch.int64, device=dev)
 
             def ptrs(ts):
                 return torch.tensor([t.data_ptr() for t in ts], dtype=torch.int64, device=dev)
-            self._tables.append(dict(params=ps, blocks=btab, nblocks=len(blocks), sizes=sizes, pp=ptrs(ps),
+            self._tables.append(dict(params=ps, blocks=btab, nblocks=nblocks, sizes=sizes, pp=ptrs(ps),
                                      m1=ptrs([self.state[p]["exp_avg"] for p in ps]),
                                      m2=ptrs([self.state[p]["exp_avg_sq"] for p in ps]), steps=steps))
         nb = sum(t["nblocks"] for t in self._tables)
