@@ -643,6 +643,33 @@ int sdp_rowscale_add_dropout(int x_dtype, int y_dtype, const void* X, int64_t ld
 int sdp_mt_cast_transpose_entry_bytes(void);
 int sdp_mt_cast_transpose(const void* entries, const void* tiles, int ntiles, void* stream);
 
+/* ---- Training input: the batch-level tail of the reference's loader, on the device ---- */
+
+/* RandomErasing + CutMix / MixUp + soft targets on a uint8 batch (hf_dataset_generator.py:43-57,
+ * :325-336; dataset_generator.py:105-110): ToDtype(float32, scale=True) -> Normalize ->
+ * RandomErasing(value 0) per image, then RandomChoice([CutMix(), MixUp(alpha=0.8)]) over the
+ * batch with the labels expanded to probability rows, in the reference's fp32 arithmetic.
+ *   images: uint8 [B][3][H][W] (nhwc 0) or [B][H][W][3] (nhwc 1), contiguous; labels: int64 [B]
+ *   (may be NULL when targets is NULL); lut: fp32 [3][256], lut[c][u] = (u / 255 - mean[c]) /
+ *   std[c]; all on the device.
+ *   plan: int32 [8 + 8 * B] on the device (one host copy): header {mode, bits(wa), bits(wp), x1,
+ *   y1, x2, y2, 0} with mode 0 none / 1 MixUp / 2 CutMix, wa / wp the fp32 weights of an image
+ *   and of its partner as bit patterns, [y1, y2) x [x1, x2) the CutMix box; then per image
+ *   {flip, top, left, h, w, 0, 0, 0}, the erase rectangle in output coordinates (flip comes
+ *   first), h == 0 or w == 0: no erase.  Plan words are only compared, never used as an index.
+ * With p = (b - 1 + B) mod B (torchvision's roll(1, 0)) and
+ *   v(i, c, y, x) = 0 inside image i's erase rectangle, else lut[c][images[i][c][y][flip_i ? W-1-x : x]]:
+ *   mode 0: out[b] = v(b);  mode 1: out[b] = fl(fl(v(p) wp) + fl(v(b) wa)) (no FMA contraction);
+ *   mode 2: out[b] = v(p) inside the box, v(b) outside.
+ *   out: [B][3][H][W] fp32 (dtype_out 0) or bf16 (1, round-to-nearest-even of the fp32 value).
+ *   targets (optional, may be NULL): fp32 [B][ldt], written only when mode != 0:
+ *   t[b][k] = fl(fl(wp [k == labels[p]]) + fl(wa [k == labels[b]])) for every k < K (ldt >= K);
+ *   labels are compared, never used as an index (a label outside [0, K) gives a row without it).
+ * The wide path (8 pixels per lane) takes NCHW with W % 8 == 0 and 8- / 16-byte aligned images /
+ * out; every other case takes an element-per-lane kernel.  B == 0 is a no-op. */
+int sdp_train_batch_aug(const uint8_t* images, int nhwc, const int64_t* labels, const float* lut,
+                        const int32_t* plan, int B, int H, int W, int dtype_out, void* out, float* targets,
+                        int64_t ldt, int K, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,11 +13,23 @@ by ``sdp_val_preprocess`` (csrc/eval.hip) straight into the model's NCHW input, 
 bf16.  The resize is Pillow's 8-bit resampler restated bit for bit (the crop's uint8
 pixels equal PIL's), so images with an aspect ratio H / W above 100 -- where Pillow
 changes its pass order -- are refused rather than approximated.
+
+Training counterpart, for the batch-level tail of the reference's ``train_transforms`` and
+collate (hf_dataset_generator.py:43-57, :325-336; dataset_generator.py:105-110):
+
+    ToImage -> ToDtype(float32, scale=True) -> Normalize -> RandomErasing(p=0.25)
+        -> RandomChoice([CutMix(), MixUp(alpha=0.8)]) -> [B, 1000] float targets
+
+The loader's workers keep decode, RandomResizedCrop and RandAugment (they work on PIL images)
+and hand over uint8 batches; ``TrainBatchTransform`` draws the random decisions on the host
+(``AugPlan``), uploads pixels, labels and plan in one copy and runs ``sdp_train_batch_aug``
+(csrc/augment.hip), which reproduces the reference's fp32 arithmetic bit for bit.
 """
 from __future__ import annotations
 
 import math
-from typing import Iterable, List, Sequence, Tuple
+from dataclasses import dataclass, field
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -125,3 +137,246 @@ def batches(dataset: Iterable, transform: ValTransform, batch_size: int = 256) -
             imgs, labels = [], []
     if imgs:
         yield transform(imgs), torch.tensor(labels, dtype=torch.int64).to(transform.device)
+
+
+# ---------------------------------------------------------------------------
+# training: RandomErasing + CutMix / MixUp + soft targets on the device
+# ---------------------------------------------------------------------------
+ERASE_SCALE = (0.02, 0.33)   # torchvision RandomErasing defaults (value 0)
+ERASE_RATIO = (0.3, 3.3)
+ERASE_ATTEMPTS = 10
+MIXUP_ALPHA = 0.8            # hf_dataset_generator.py:325-336: RandomChoice([CutMix(), MixUp(alpha=0.8)])
+CUTMIX_ALPHA = 1.0
+MODE_NONE, MODE_MIXUP, MODE_CUTMIX = 0, 1, 2
+
+
+def normalize_lut(mean=IMAGENET_MEAN, std=IMAGENET_STD) -> torch.Tensor:
+    """fp32 [3, 256]: ToDtype(float32, scale=True) + Normalize of every uint8 value, with the
+    expression of the evaluation oracle, so that table look-up equals the fp32 ops bit for bit."""
+    u = torch.arange(256, dtype=torch.float32) / 255.0
+    return torch.stack([(u - float(mean[c])) / float(std[c]) for c in range(3)]).contiguous()
+
+
+def cutmix_box(lam: float, r_x: int, r_y: int, H: int, W: int) -> Tuple[Tuple[int, int, int, int], float]:
+    """torchvision CutMix: ((x1, y1, x2, y2), lam_adjusted) of the box centred on (r_x, r_y)."""
+    r = 0.5 * math.sqrt(1.0 - lam)
+    r_w_half, r_h_half = int(r * W), int(r * H)
+    x1, y1 = max(r_x - r_w_half, 0), max(r_y - r_h_half, 0)
+    x2, y2 = min(r_x + r_w_half, W), min(r_y + r_h_half, H)
+    return (x1, y1, x2, y2), float(1.0 - (x2 - x1) * (y2 - y1) / (W * H))
+
+
+def mix_weights(lam: float) -> Tuple[float, float]:
+    """(wa, wp): the fp32 weights of an image and of its partner, as torch rounds the Python
+    scalars of ``x.roll(1, 0).mul(1.0 - lam).add_(x.mul(lam))`` (the subtraction in double)."""
+    f32 = lambda v: float(np.float32(v))  # noqa: E731
+    return f32(lam), f32(1.0 - lam)
+
+
+@dataclass
+class AugPlan:
+    """The random decisions of one training batch, as plain host data.
+
+    flip [B] (0 / 1), erase [B, 4] (top, left, h, w in output coordinates; h == 0 or w == 0: no
+    erase), mode (0 none, 1 MixUp, 2 CutMix), wa / wp (the weights of an image and of its partner
+    ``(b - 1) mod B``, exact fp32 values), box (x1, y1, x2, y2)."""
+    B: int
+    H: int
+    W: int
+    flip: np.ndarray
+    erase: np.ndarray
+    mode: int = MODE_NONE
+    lam: float = 1.0
+    wa: float = 1.0
+    wp: float = 0.0
+    box: Tuple[int, int, int, int] = field(default=(0, 0, 0, 0))
+
+    @staticmethod
+    def identity(B: int, H: int, W: int) -> "AugPlan":
+        return AugPlan(B, H, W, np.zeros(B, np.int32), np.zeros((B, 4), np.int32))
+
+    @staticmethod
+    def sample(B: int, H: int, W: int, generator: Optional[torch.Generator] = None, mix: Optional[str] = "reference",
+               erase_p: float = 0.25, flip_p: float = 0.0) -> "AugPlan":
+        """Draw a plan from torch's CPU generator; the same seed gives the same plan.
+
+        Per image: flip with probability ``flip_p``; RandomErasing with probability ``erase_p``
+        and torchvision's defaults: up to 10 attempts of area = H W U(0.02, 0.33), aspect =
+        exp(U(log 0.3, log 3.3)), h = round(sqrt(area aspect)), w = round(sqrt(area / aspect)),
+        the first with h < H and w < W taken, then top ~ U{0..H-h}, left ~ U{0..W-w}; no erase
+        if none fits.  Per batch (``mix="reference"``): CutMix (alpha 1.0) or MixUp (alpha 0.8)
+        with equal probability, lam ~ Beta(alpha, alpha) in fp32 as torchvision draws it.
+        The draws of a batch are taken in bulk (a fixed number per image), so the stream is not
+        torchvision's; the distribution and the formulas are."""
+        if mix not in (None, "reference"):
+            raise ValueError(f"mix must be 'reference' or None, got {mix!r}")
+        g = generator
+        per = torch.rand(B, 4 + 2 * ERASE_ATTEMPTS, generator=g, dtype=torch.float64).numpy()
+        flip = (per[:, 0] < flip_p).astype(np.int32)
+        erase = np.zeros((B, 4), np.int32)
+        s0, s1 = ERASE_SCALE
+        l0, l1 = math.log(ERASE_RATIO[0]), math.log(ERASE_RATIO[1])
+        for b in np.nonzero(per[:, 1] < erase_p)[0]:
+            for a in range(ERASE_ATTEMPTS):
+                area = H * W * (s0 + (s1 - s0) * per[b, 4 + 2 * a])
+                aspect = math.exp(l0 + (l1 - l0) * per[b, 5 + 2 * a])
+                h, w = int(round(math.sqrt(area * aspect))), int(round(math.sqrt(area / aspect)))
+                if not (h < H and w < W):
+                    continue
+                top = min(int(per[b, 2] * (H - h + 1)), H - h)
+                left = min(int(per[b, 3] * (W - w + 1)), W - w)
+                erase[b] = (top, left, h, w)
+                break
+        plan = AugPlan(B, H, W, flip, erase)
+        if mix is None:
+            return plan
+        pick = torch.rand(1, generator=g).item()
+        alpha = CUTMIX_ALPHA if pick < 0.5 else MIXUP_ALPHA
+        lam = float(torch._sample_dirichlet(torch.tensor([alpha, alpha]), g)[0])
+        if pick < 0.5:
+            r_x = int(torch.randint(W, (1,), generator=g))
+            r_y = int(torch.randint(H, (1,), generator=g))
+            return plan.with_cutmix(lam, r_x, r_y)
+        return plan.with_mixup(lam)
+
+    def with_mixup(self, lam: float) -> "AugPlan":
+        self.mode, self.lam, self.box = MODE_MIXUP, float(lam), (0, 0, 0, 0)
+        self.wa, self.wp = mix_weights(lam)
+        return self
+
+    def with_cutmix(self, lam: float, r_x: int, r_y: int) -> "AugPlan":
+        self.box, lam_adj = cutmix_box(lam, r_x, r_y, self.H, self.W)
+        self.mode, self.lam = MODE_CUTMIX, lam_adj
+        self.wa, self.wp = mix_weights(lam_adj)
+        return self
+
+    def words(self) -> int:
+        return sp.AUG_PLAN_HEADER + sp.AUG_PLAN_PER_IMAGE * self.B
+
+    def pack(self, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """The int32 words sdp_train_batch_aug reads (layout: include/sdpnet_hip.h)."""
+        if out is None:
+            out = np.empty(self.words(), np.int32)
+        out[:] = 0
+        out[0] = self.mode
+        out[1:3] = np.array([self.wa, self.wp], np.float32).view(np.int32)
+        out[3:7] = self.box
+        per = out[sp.AUG_PLAN_HEADER:].reshape(self.B, sp.AUG_PLAN_PER_IMAGE)
+        per[:, 0] = self.flip
+        per[:, 1:5] = self.erase
+        return out
+
+
+class _Staging:
+    """One pinned upload buffer and the event recorded after its last copy."""
+
+    def __init__(self):
+        self.buf: Optional[torch.Tensor] = None
+        self.event: Optional[torch.cuda.Event] = None
+
+    def take(self, nbytes: int) -> torch.Tensor:
+        if self.event is not None:
+            self.event.synchronize()  # the copy out of this buffer, two batches ago
+        if self.buf is None or self.buf.numel() < nbytes:
+            self.buf = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+        return self.buf[:nbytes]
+
+
+def _round_up(n: int, a: int) -> int:
+    return (n + a - 1) // a * a
+
+
+class TrainBatchTransform:
+    """The reference's training tail on a uint8 batch: ``__call__(images_u8, labels, plan=None)
+    -> (images [B, 3, H, W] of ``dtype`` on ``device``, targets)``.  targets are the fp32
+    [B, num_classes] probability rows, or the int64 labels when the plan does not mix.
+
+    images_u8 ([B, 3, H, W], or [B, H, W, 3] with ``channels_last``) and labels may each live on
+    the host or on the device.  Whatever is on the host is packed behind the plan into one of two
+    alternating pinned buffers and uploaded with one copy; a buffer is reused only after the event
+    recorded behind its copy, so the only host wait is on a copy from two batches earlier and
+    nothing synchronises the device."""
+
+    def __init__(self, num_classes: int = 1000, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda",
+                 dtype=torch.float32, mix: Optional[str] = "reference", erase_p: float = 0.25, flip_p: float = 0.0,
+                 channels_last: bool = False, generator: Optional[torch.Generator] = None):
+        self.num_classes = int(num_classes)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("TrainBatchTransform runs sdp_train_batch_aug; the HIP path has no CPU fallback")
+        sp.dcode(dtype)
+        self.dtype = dtype
+        self.mix, self.erase_p, self.flip_p = mix, float(erase_p), float(flip_p)
+        self.channels_last = bool(channels_last)
+        self.generator = generator
+        self.lut = normalize_lut(mean, std).to(self.device)
+        self._staging = (_Staging(), _Staging())
+        self._turn = 0
+
+    def sample(self, B: int, H: int, W: int) -> AugPlan:
+        return AugPlan.sample(B, H, W, self.generator, self.mix, self.erase_p, self.flip_p)
+
+    def __call__(self, images_u8: torch.Tensor, labels: torch.Tensor, plan: Optional[AugPlan] = None):
+        if images_u8.dtype != torch.uint8 or images_u8.dim() != 4:
+            raise TypeError(f"training batches are uint8 [B, 3, H, W] / [B, H, W, 3], got {images_u8.dtype} "
+                            f"{tuple(images_u8.shape)}")
+        B = images_u8.shape[0]
+        H, W = images_u8.shape[1:3] if self.channels_last else images_u8.shape[2:4]
+        labels = labels.to(torch.int64)
+        if labels.shape != (B,):
+            raise ValueError(f"labels must be [B] = [{B}], got {tuple(labels.shape)}")
+        if plan is None:
+            plan = self.sample(B, H, W)
+        if (plan.B, plan.H, plan.W) != (B, H, W):
+            raise ValueError(f"plan is for {(plan.B, plan.H, plan.W)}, the batch is {(B, H, W)}")
+        labels_host = None if labels.is_cuda else labels
+        if labels_host is not None and B and not (0 <= int(labels_host.min()) and int(labels_host.max()) < self.num_classes):
+            raise ValueError(f"label outside [0, {self.num_classes})")
+        # one pinned buffer: plan words | host labels | host pixels (16-byte aligned sections)
+        n_plan = 4 * plan.words()
+        o_lab = _round_up(n_plan, 16)
+        o_img = _round_up(o_lab + (0 if labels.is_cuda else 8 * B), 16)
+        total = o_img + (0 if images_u8.is_cuda else images_u8.numel())
+        st = self._staging[self._turn]
+        self._turn ^= 1
+        host = st.take(total)
+        plan.pack(host[:n_plan].view(torch.int32).numpy())
+        if not labels.is_cuda:
+            host[o_lab:o_lab + 8 * B].view(torch.int64).copy_(labels)
+        if not images_u8.is_cuda:
+            host[o_img:].view(images_u8.shape).copy_(images_u8)
+        with torch.cuda.device(self.device):
+            dev = host.to(self.device, non_blocking=True)
+            st.event = torch.cuda.Event()
+            st.event.record()
+        plan_d = dev[:n_plan].view(torch.int32)
+        labels_d = labels if labels.is_cuda else dev[o_lab:o_lab + 8 * B].view(torch.int64)
+        images_d = images_u8.contiguous() if images_u8.is_cuda else dev[o_img:].view(images_u8.shape)
+        mixed = plan.mode != MODE_NONE
+        out, targets = sp.train_batch_aug(images_d, labels_d, self.lut, plan_d, self.num_classes, self.dtype, mixed,
+                                          channels_last=self.channels_last)
+        if mixed:
+            return out, targets
+        # uploaded labels are a view of the upload; a copy lets the pixels' memory go
+        return out, (labels_d if labels.is_cuda else labels_d.clone())
+
+
+class DeviceAugLoader:
+    """Wraps a loader of (uint8 images, int labels) host batches into an iterable of
+    (images, targets) device batches: drops into ``Trainer(train_data=...)`` (its ``.to(gpu_id)``
+    on the batches is then a no-op; ``len()`` and ``.sampler`` are the loader's)."""
+
+    def __init__(self, loader, transform: TrainBatchTransform):
+        self.loader = loader
+        self.transform = transform
+
+    def __len__(self) -> int:
+        return len(self.loader)
+
+    @property
+    def sampler(self):
+        return self.loader.sampler
+
+    def __iter__(self):
+        for images, labels in self.loader:
+            yield self.transform(images, labels)

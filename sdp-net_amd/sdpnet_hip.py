@@ -141,6 +141,8 @@ _SIGS = {
     "sdp_attn_train_bwd": ([_i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32,
                             _i32, _i32, _i32, _f32, _f32, _u64, _vp], _i32),
     "sdp_attn_dropout_mask": ([_vp, _i32, _i32, _f32, _u64, _vp], _i32),
+    # training input (augment.hip)
+    "sdp_train_batch_aug": ([_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp], _i32),
 }
 
 _lib = None
@@ -1095,3 +1097,62 @@ def attn_dropout_mask(Z: int, N: int, p: float, seed: int, device) -> torch.Tens
     _check(lib().sdp_attn_dropout_mask(out.data_ptr(), Z, N, float(p), int(seed) & 0xFFFFFFFFFFFFFFFF, _stream(out)),
            "attn_dropout_mask")
     return out
+
+
+# ---------------------------------------------------------------------------
+# training input (augment.hip)
+# ---------------------------------------------------------------------------
+AUG_PLAN_HEADER, AUG_PLAN_PER_IMAGE = 8, 8  # int32 words of the plan: header, then per image
+
+
+def train_batch_aug(images: torch.Tensor, labels: Optional[torch.Tensor], lut: torch.Tensor, plan: torch.Tensor,
+                    num_classes: int, dtype: torch.dtype, mixed: bool, channels_last: bool = False,
+                    targets: Optional[torch.Tensor] = None, labels_host: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None):
+    """RandomErasing + CutMix / MixUp + soft targets on a uint8 batch (sdp_train_batch_aug).
+
+    images uint8 [B, 3, H, W], or [B, H, W, 3] with ``channels_last``; labels int64 [B]; lut fp32
+    [3, 256]; plan int32 [8 + 8 B] (layout: include/sdpnet_hip.h), all on the device.  ``mixed``
+    says whether the plan's mode is MixUp / CutMix: the probability rows [B, num_classes] fp32 are
+    produced then (into ``targets`` when given: fp32, unit column stride, row stride >=
+    num_classes).  ``labels_host``: the same labels on the host, range-checked against
+    [0, num_classes) before the launch (device labels are only compared in the kernel, never used
+    as an index).  Returns (out [B, 3, H, W] of ``dtype`` -- ``out`` itself when given --, targets
+    or None)."""
+    dt = dcode(dtype)
+    _req(images.dtype == torch.uint8 and images.dim() == 4 and images.is_contiguous(), "train_batch_aug images uint8")
+    B = images.shape[0]
+    if channels_last:
+        H, W, C = images.shape[1:]
+    else:
+        C, H, W = images.shape[1:]
+    _req(C == 3 and H > 0 and W > 0, "train_batch_aug images are RGB")
+    _req(lut.dtype == torch.float32 and tuple(lut.shape) == (3, 256) and lut.is_contiguous(), "train_batch_aug lut")
+    _req(plan.dtype == torch.int32 and plan.is_contiguous() and
+         plan.numel() >= AUG_PLAN_HEADER + AUG_PLAN_PER_IMAGE * B, "train_batch_aug plan")
+    K = int(num_classes)
+    if mixed:
+        _req(K > 0, "train_batch_aug num_classes")
+        _req(labels is not None and labels.dtype == torch.int64 and labels.is_contiguous() and labels.numel() == B,
+             "train_batch_aug labels int64 [B]")
+        if targets is not None:
+            _req(targets.dtype == torch.float32 and targets.dim() == 2 and targets.shape[0] == B and
+                 targets.shape[1] >= K and (B <= 1 or targets.stride(0) >= K) and targets.stride(1) == 1,
+                 "train_batch_aug targets fp32 [B, >= num_classes]")
+    else:
+        _req(targets is None, "train_batch_aug targets need a mixing plan")
+    if labels_host is not None and labels_host.numel():
+        lo, hi = int(labels_host.min()), int(labels_host.max())
+        _req(0 <= lo and hi < K, f"train_batch_aug label outside [0, {K})")
+    _req(out is None or (out.dtype == dtype and tuple(out.shape) == (B, 3, H, W) and out.is_contiguous()),
+         "train_batch_aug out [B, 3, H, W] of dtype")
+    _need_cuda(images, labels, lut, plan, targets, out)
+    if out is None:
+        out = torch.empty(B, 3, H, W, dtype=dtype, device=images.device)
+    if mixed and targets is None:
+        targets = torch.empty(B, K, dtype=torch.float32, device=images.device)
+    rc = lib().sdp_train_batch_aug(images.data_ptr(), int(bool(channels_last)), _ptr(labels) if mixed else None,
+                                   lut.data_ptr(), plan.data_ptr(), B, H, W, dt, out.data_ptr(), _ptr(targets),
+                                   targets.stride(0) if (mixed and B > 1) else K, K, _stream(out))
+    _check(rc, "train_batch_aug")
+    return out, targets
