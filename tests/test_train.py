@@ -8,10 +8,15 @@ fp32 (exact MFMA) and bf16 (autocast, the reference's training dtype), then our 
 AdamW (+ clip_grad_norm_) step; dropout / drop path statistics and mask consistency; a
 gloo world-size-2 DDP run whose averaged gradient equals the single-process gradient.
 
-Tolerances: fp32 gradients within 1e-4 of each tensor's max |g| (relative), loss 1e-5;
-bf16 gradients (fp32 residual stream, the default) within 2x the reference's own
-CPU-autocast-bf16 gradient error + 4e-2 AND within 4x that error (relative); the all-bf16
-stream option within 2x + 6e-2; AdamW parameters 1e-5 absolute (fp32).
+Tolerances: fp32 gradients per tensor within 1e-4 of that tensor's own max |g|, with no
+model-wide floor (tests/grad_judge.py; k_norm.bias, whose exact gradient is zero, is judged
+against its layer's k_norm.weight), loss 1e-5.  bf16 gradients (fp32 residual stream, the
+default): each tensor's error, over max(|g|max, 1e-3 of the model's largest gradient), within
+2x the reference's own CPU-autocast-bf16 error (same measure) + 4e-2 in the fixture test, and
+within min(that, 4x the autocast error) in the XL test only; the all-bf16 stream option within
+2x + 6e-2.  The floor in the bf16 measure hides small tensors (an all-zero gradient passes for
+50 of train_cf's 88): tests/test_gpu_train_matrix.py judges bf16 per tensor without it.
+AdamW parameters 1e-5 absolute (fp32).
 """
 import json
 import os
@@ -22,6 +27,7 @@ import torch
 import torch.nn.functional as F
 
 import golden_util as gu
+import grad_judge as gj
 import sdpnet_oracle as orc
 import synth
 
@@ -44,9 +50,10 @@ def _case(name):
 
 def _rel(got, ref, floor=0.0):
     """max |got - ref| over max(|ref|.max(), floor).  ``floor`` (a fraction of the largest
-    gradient of the model) keeps tensors whose exact gradient is zero -- k_norm.bias: a bias
-    added to every key shifts all scores of a query equally, so softmax ignores it -- from
-    being judged on rounding noise."""
+    gradient of the model) is used by the bf16 budgets only; it keeps tensors whose exact gradient
+    is zero -- k_norm.bias: a bias added to every key shifts all scores of a query equally, so
+    softmax ignores it -- from being judged on rounding noise, and hides every other small tensor
+    with it.  The fp32 checks use the per-tensor rule of tests/grad_judge.py instead."""
     return float(np.abs(got - ref).max()) / max(1e-12, float(np.abs(ref).max()), floor)
 
 
@@ -62,10 +69,12 @@ def test_oracle_gradients_match_reference_fixture(name):
     loss = F.cross_entropy(logits, y, label_smoothing=meta["label_smoothing"])
     loss.backward()
     assert abs(float(loss) - float(arr["loss"])) <= 1e-5
-    for k, _ in m.named_parameters():
-        g = osd[k].grad
-        assert g is not None, k
-        assert _rel(g.numpy(), arr["grad/" + k], _floor(arr)) <= 1e-5, k
+    names = [k for k, _ in m.named_parameters()]
+    assert all(osd[k].grad is not None for k in names)
+    # per tensor, 1e-5 of its own largest gradient (no model-wide floor)
+    bad = gj.fp32_failures({k: osd[k].grad for k in names}, {k: arr["grad/" + k] for k in names},
+                           gj.qv_layers(meta["config"]), names, tol=1e-5)
+    assert not bad, bad[:4]
 
 
 def _train_step(name, bf16, fp32_stream=True):
@@ -92,8 +101,10 @@ def _train_step(name, bf16, fp32_stream=True):
 @pytest.mark.parametrize("name", CASES)
 @pytest.mark.parametrize("mode", ["fp32", "bf16", "bf16_stream16"])
 def test_gradients_match_reference(name, mode):
-    """fp32: every gradient within 1e-4 (relative) of the reference's fp32 gradient.  bf16
-    (autocast, fp32 residual stream and stream gradient as autocast keeps them): each tensor's
+    """fp32: every gradient within 1e-4 of its own tensor's largest reference gradient (the fp32
+    rule of tests/grad_judge.py, no model-wide floor; the stored fp32 references are themselves
+    within 2e-6 of fp64 judged this way).  bf16 (autocast, fp32 residual stream and stream
+    gradient as autocast keeps them), numbers unchanged, with the model-wide floor: each tensor's
     error within 2x the reference's OWN CPU-autocast-bf16 gradient error on the same inputs
     (grad_ac/* in the fixture) + 4e-2.  One tensor of the ReLU case, the first block's
     ff_linear1.weight, sits at 6x the CPU-autocast error (2.3e-2 vs 3.8e-3; 4.1x the same
@@ -104,14 +115,24 @@ def test_gradients_match_reference(name, mode):
     bf16 = mode != "fp32"
     meta, arr, m, logits, loss = _train_step(name, bf16, fp32_stream=mode != "bf16_stream16")
     assert abs(float(loss) - float(arr["loss"])) <= (2e-2 if bf16 else 1e-5), (float(loss), float(arr["loss"]))
-    fl = _floor(arr)
-    worst = []
     for k, p in m.named_parameters():
         assert p.grad is not None, f"{k}: no gradient"
         assert p.grad.dtype == torch.float32 and p.grad.shape == p.shape
+    if mode == "fp32":
+        names = [k for k, _ in m.named_parameters()]
+        got = {k: p.grad for k, p in m.named_parameters()}
+        ref = {k: arr["grad/" + k] for k in names}
+        rows, _ = gj.fp32_report(got, ref, names)
+        print(f"{name} fp32: loss {float(loss):.6f} (ref {float(arr['loss']):.6f}); worst grads (of 1e-4 of own max) "
+              + ", ".join(f"{k} {r:.2e}" for r, _, _, k in rows[:4]))
+        gj.assert_fp32(got, ref, gj.qv_layers(meta["config"]), names, name)
+        return
+    fl = _floor(arr)  # bf16 only (numbers kept as they were)
+    worst = []
+    for k, p in m.named_parameters():
         r = _rel(p.grad.cpu().numpy(), arr["grad/" + k], fl)
         rref = _rel(arr["grad_ac/" + k], arr["grad/" + k], fl)
-        tol = {"fp32": 1e-4, "bf16": 2 * rref + 4e-2, "bf16_stream16": 2 * rref + 6e-2}[mode]
+        tol = {"bf16": 2 * rref + 4e-2, "bf16_stream16": 2 * rref + 6e-2}[mode]
         worst.append((r / tol, r, rref, k))
     worst.sort(reverse=True)
     print(f"{name} {mode}: loss {float(loss):.6f} (ref {float(arr['loss']):.6f}); worst grads "
@@ -400,10 +421,11 @@ def test_full_size_row_counts_against_oracle():
     F.cross_entropy(orc.forward.__wrapped__(x, osd, cfg), y, label_smoothing=0.1).backward()
     m = m.to(DEV).train()
     sdpnet_train.cross_entropy(m(x.to(DEV)), y.to(DEV), 0.1).backward()
-    fl = 1e-3 * max(float(osd[k].grad.abs().max()) for k, _ in m.named_parameters())
-    worst = max((_rel(p.grad.cpu().numpy(), osd[k].grad.numpy(), fl), k) for k, p in m.named_parameters())
-    print("full-size rows: worst fp32 grad rel err", worst)
-    assert worst[0] <= 1e-4, worst
+    names = [k for k, _ in m.named_parameters()]
+    got, ref = {k: p.grad for k, p in m.named_parameters()}, {k: osd[k].grad for k in names}
+    rows, _ = gj.fp32_report(got, ref, names)
+    print("full-size rows: worst fp32 grads (of 1e-4 of own max)", [(k, f"{r:.2e}") for r, _, _, k in rows[:3]])
+    gj.assert_fp32(got, ref, gj.qv_layers(cfg), names, "full-size rows")
 
 
 @pytest.mark.gpu
@@ -439,11 +461,11 @@ def test_train_mode_embedding_activation_and_raw_outputs(conv_emb):
     assert xg.shape == xo.shape and rg.shape == ro.shape
     assert float((xg.cpu() - xo.detach()).abs().max()) <= 1e-4
     objective(lg, xg, rg).backward()
-    fl = 1e-3 * max(float(osd[k].grad.abs().max()) for k, _ in m.named_parameters())
-    worst = max((_rel(p.grad.cpu().numpy(), osd[k].grad.numpy(), fl), k) for k, p in m.named_parameters())
-    assert worst[0] <= 1e-4, worst
+    names = [k for k, _ in m.named_parameters()]
+    gj.assert_fp32({k: p.grad for k, p in m.named_parameters()}, {k: osd[k].grad for k in names},
+                   gj.qv_layers(cfg), names, "raw outputs")
     assert xd.grad is not None and xd.grad.shape == xr.grad.shape
-    assert _rel(xd.grad.cpu().numpy(), xr.grad.numpy(), 1e-3 * float(xr.grad.abs().max())) <= 1e-4
+    assert _rel(xd.grad.cpu().numpy(), xr.grad.numpy()) <= 1e-4
 
 
 XL_TRAIN_CFG = dict(embedding_dim=768, num_blocks=2, n_head=8, conv_kernel_size=7, patch_size=14,
@@ -456,8 +478,9 @@ XL_TRAIN_CFG = dict(embedding_dim=768, num_blocks=2, n_head=8, conv_kernel_size=
 def test_xl_architecture_training_step_against_oracle():
     """BASELINE.json configs[4]'s architecture (training_tools.py:77-103): SdP-Net-XL's block
     dimensions -- d 768, 8 heads of 96, patch 14, 256 patches + 4 registers = 260 tokens -- with
-    2 blocks to keep the CPU side cheap, batch 2.  fp32: every HIP gradient within 1e-4 (relative)
-    of autograd through the oracle (pinned by the train fixtures); the fused AdamW step equals
+    2 blocks to keep the CPU side cheap, batch 2.  fp32: every HIP gradient within 1e-4 of its own
+    tensor's largest gradient from autograd through the oracle (pinned by the train fixtures; the
+    per-tensor fp32 rule of tests/grad_judge.py, no model-wide floor); the fused AdamW step equals
     torch.optim.AdamW + clip_grad_norm_ on the same gradients.  bf16 (autocast, fp32 residual
     stream): each gradient's error within min(2x the oracle's own CPU-autocast error + 4e-2, 4x
     that error) (the fixture rule)."""
@@ -484,11 +507,17 @@ def test_xl_architecture_training_step_against_oracle():
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bf16):
             loss = sdpnet_train.cross_entropy(m(x.to(DEV)), y.to(DEV), 0.1)
         loss.backward()
+        if not bf16:
+            got = {k: p.grad for k, p in m.named_parameters()}
+            rows, _ = gj.fp32_report(got, ref, list(ref))
+            print("XL-dim training fp32: worst (of 1e-4 of own max)", [(k, f"{r:.2e}") for r, _, _, k in rows[:3]])
+            gj.assert_fp32(got, ref, gj.qv_layers(cfg), list(ref), "XL fp32")
+            continue
         worst = []
         for k, p in m.named_parameters():
             r = _rel(p.grad.cpu().numpy(), ref[k], fl)
             rac = _rel(asd[k].grad.float().numpy(), ref[k], fl)
-            tol = min(2 * rac + 4e-2, 4 * rac) if bf16 else 1e-4
+            tol = min(2 * rac + 4e-2, 4 * rac)
             worst.append((r / tol, r, rac, k))
         worst.sort(reverse=True)
         print(f"XL-dim training bf16={bf16}: worst", [(k, f"{r:.2e}", f"{rac:.2e}") for _, r, rac, k in worst[:3]])
@@ -680,9 +709,11 @@ def _run_two_ranks(gpu):
         for p in procs:
             p.join(timeout=60)
     assert all(p.exitcode == 0 for p in procs)
-    _, arr = gu.load_case(CASES[0])
-    worst = max(_rel(g, arr["grad/" + k], _floor(arr)) for k, g in grads.items())
-    return worst
+    meta, arr = gu.load_case(CASES[0])
+    # worst error over tensors, each relative to its own largest gradient (tests/grad_judge.py, no floor)
+    rows, exempt = gj.fp32_report(grads, {k: arr["grad/" + k] for k in grads}, tol=1.0)
+    assert len(exempt) == gj.qv_layers(meta["config"])
+    return rows[0][0]
 
 
 def test_two_rank_ddp_gradient_average_matches_single_process():
