@@ -238,7 +238,8 @@ int sdp_dwconv_set_kernel(int k);
  * applies it in place on the QKV rows.  mask: optional fp32 additive [.., N, N]
  * with batch / head strides (0 = broadcast).  Replaces q_norm/k_norm and
  * F.scaled_dot_product_attention (layers.py:286-291) and the manual softmax path
- * (layers.py:292-298).
+ * (layers.py:292-298).  The MFMA kernels keep the byte offsets inside one image in 32 bits:
+ * roundup(N, 16) * ld_qkv * 2 >= 2^32 returns hipErrorInvalidValue (nothing is launched).
  */
 int sdp_attention(int dtype, const void* QKV, int64_t ld_qkv, void* O, int64_t ld_o, int B, int N,
                   int n_head, int head_dim, const float* q_gamma, const float* q_beta,

@@ -1826,6 +1826,10 @@ extern "C" int sdp_attention(int dtype, const void* QKV, int64_t ldq, void* O, i
   const float scale = 1.0f / sqrtf((float)head_dim);
   const bool al = (ldq % 8 == 0) && (ldo % 4 == 0) && ((uintptr_t)QKV % 16 == 0) && ((uintptr_t)O % 8 == 0);
   const int variant = al ? sdp_attention_variant(dtype, N, n_head, head_dim, mask != nullptr) : 0;
+  // AttnKV (variants 3, 4, 6) keeps the K / V byte offsets within one image in 32 bits: the padded
+  // image's QKV rows must span less than 2^32 bytes
+  if ((variant == 3 || variant == 4 || variant == 6) && ((int64_t)(N + 15) / 16 * 16) * ldq * 2 >= (1ll << 32))
+    return (int)hipErrorInvalidValue;
   if (variant == 5) {
     const float *gq = norm ? q_gamma : nullptr, *bq = norm ? q_beta : nullptr;
     const float *gk = norm ? k_gamma : nullptr, *bk = norm ? k_beta : nullptr;
