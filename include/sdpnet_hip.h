@@ -245,6 +245,15 @@ int sdp_attention(int dtype, const void* QKV, int64_t ld_qkv, void* O, int64_t l
                   int n_head, int head_dim, const float* q_gamma, const float* q_beta,
                   const float* k_gamma, const float* k_beta, float eps, const float* mask,
                   int64_t mask_sb, int64_t mask_sh, void* stream);
+/* sdp_attention for a caller that reads only output rows [0, q_rows) of every image (q_rows >= 1):
+ * those rows equal sdp_attention's bit for bit; rows at or past q_rows may or may not be written.
+ * K / V staging and the k-norm cover all N keys.  attn_fa4 and attn_fa6 compute only the query
+ * tiles (32 rows) that intersect the range, every other kernel computes all rows.  q_rows >= N is
+ * sdp_attention. */
+int sdp_attention_rows(int dtype, const void* QKV, int64_t ld_qkv, void* O, int64_t ld_o, int B, int N,
+                       int n_head, int head_dim, const float* q_gamma, const float* q_beta,
+                       const float* k_gamma, const float* k_beta, float eps, const float* mask,
+                       int64_t mask_sb, int64_t mask_sh, int q_rows, void* stream);
 /* Kernel sdp_attention takes for this shape: 6 = attn_fa5, one double-buffered 8-wave workgroup per
  * CU (diagnostic build only, opt-in, hd % 32 == 0, N <= 224), 4 = two persistent 4-wave flash workgroups per CU, one LDS-DMA
  * K/V buffer each (hd % 32 == 0, N <= 256), 3 = whole-head flash kernels (hd % 32 == 0, head within

@@ -977,12 +977,12 @@ static size_t attn_fa6_bytes(int N, int hd);
 template <int HDT>
 static int launch_attn_fa6(const void* QKV, int64_t ldq, void* O, int64_t ldo, int B, int N, int H,
                            const float* gq, const float* bq, const float* gk, const float* bk, float eps, float scale,
-                           hipStream_t s);
+                           int q_rows, hipStream_t s);
 
 template <int HDT>
 static int launch_attn_fa2(const void* QKV, int64_t ldq, void* O, int64_t ldo, int B, int N, int H,
                            const float* gq, const float* bq, const float* gk, const float* bk, float eps, float scale,
-                           hipStream_t s) {
+                           int q_rows, hipStream_t s) {
   size_t bytes = attn_fa2_bytes(N, 32 * HDT);
   // one query tile per wave up to 9 tiles (N <= 288: XL's 260 tokens are 8 full tiles + 4 rows;
   // with 8 waves one wave did two tiles and set the block's time), else 8 waves looping; at exactly
@@ -994,7 +994,7 @@ static int launch_attn_fa2(const void* QKV, int64_t ldq, void* O, int64_t ldo, i
   const void* fn = split ? (const void*)attn_fa2_bf16<HDT, HDT <= 3 ? 9 : 0> : (const void*)attn_fa2_bf16<HDT, 0>;
   if constexpr (HDT <= 3)
     if (split && attn_fa6_bytes(N, 32 * HDT) <= 160 * 1024)  // persistent form, K / V staging hidden
-      return launch_attn_fa6<HDT>(QKV, ldq, O, ldo, B, N, H, gq, bq, gk, bk, eps, scale, s);
+      return launch_attn_fa6<HDT>(QKV, ldq, O, ldo, B, N, H, gq, bq, gk, bk, eps, scale, q_rows, s);
   if (split) {
     waves = 11;
     bytes += (size_t)3 * (N - 256) * (32 * HDT + 4) * 4;
@@ -1082,12 +1082,17 @@ __device__ unsigned long long g_attn_stamps[1024 * 2 * 8 * 5];
 #define SDP_ASTAMP5(j, k) do {} while (0)
 #define SDP_ASTAMP6(j, k) do {} while (0)
 #endif
-template <int HDT, int NKT>
+// LIM: only the query tiles that intersect rows [0, q_rows) of each image are computed
+// (sdp_attention_rows, q_rows < N): K / V staging and the k-norm still cover all N keys, a wave
+// whose tile lies past the limit only stages, normalises and waits at the barriers, and a computed
+// tile runs the same attn_qtile_chunked on the same rows (its Q loaded directly: with most slots
+// gone there is no prefetch chain), so its output rows equal the full kernel's bit for bit.
+template <int HDT, int NKT, bool LIM = false>
 __global__ __launch_bounds__(256, 2) void attn_fa4_bf16(const bf16_t* __restrict__ QKV, int64_t ldq,
                                                      bf16_t* __restrict__ O, int64_t ldo, int B, int N, int H,
                                                      const float* __restrict__ gq, const float* __restrict__ bq,
                                                      const float* __restrict__ gk, const float* __restrict__ bk,
-                                                     float eps, float scale_log2) {
+                                                     float eps, float scale_log2, int q_rows) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   constexpr int HD = 32 * HDT;
   const int NP16 = (N + 15) / 16 * 16;
@@ -1133,7 +1138,7 @@ __global__ __launch_bounds__(256, 2) void attn_fa4_bf16(const bf16_t* __restrict
   const int64_t off0 = (int64_t)(ok0 ? q0 : N - 1) * ldq, off1 = (int64_t)(ok1 ? q1 : N - 1) * ldq;
   bf16x8 qa[2 * HDT], qb[2 * HDT];
   int pair = pair_of(0);
-  attn_load_q<HDT>(qkv_base(pair) + off0, hf, qa);
+  if constexpr (!LIM) attn_load_q<HDT>(qkv_base(pair) + off0, hf, qa);
   for (int j = 0; j < nj; ++j) {
     const int nxt = j + 1 < nj ? pair_of(j + 1) : pair;  // last pair: a harmless re-load
     SDP_ASTAMP(j, 0);
@@ -1150,6 +1155,24 @@ __global__ __launch_bounds__(256, 2) void attn_fa4_bf16(const bf16_t* __restrict
     SDP_ASTAMP(j, 2);
     const int b = pair / H, hh = pair - (pair / H) * H;
     bf16_t* obase = O + (int64_t)b * N * ldo + hh * HD;
+    if constexpr (LIM) {
+      const int uw = __builtin_amdgcn_readfirstlane(wave);
+      if (32 * uw < q_rows) {
+        attn_load_q<HDT>(qkv_base(pair) + off0, hf, qa);
+        if (norm) attn_norm_q<HDT>(qa, ok0, hf, prm, prm + HD, eps);
+        attn_qtile_chunked<HDT, NKT, (HDT <= 3 ? ATTN_CH : 4), false>(Ks, Vs, qa, N, scale_log2, lane,
+                                                                      ok0 ? obase + q0 * ldo : nullptr, nullptr, qa);
+      }
+      if (32 * (uw + 4) < q_rows) {
+        attn_load_q<HDT>(qkv_base(pair) + off1, hf, qb);
+        if (norm) attn_norm_q<HDT>(qb, ok1, hf, prm, prm + HD, eps);
+        attn_qtile_chunked<HDT, NKT, (HDT <= 3 ? ATTN_CH : 4), false>(Ks, Vs, qb, N, scale_log2, lane,
+                                                                      ok1 ? obase + q1 * ldo : nullptr, nullptr, qb);
+      }
+      pair = nxt;
+      __syncthreads();
+      continue;
+    }
     // slot 0 (query tile w), prefetching slot 1's Q
     if (norm) attn_norm_q<HDT>(qa, ok0, hf, prm, prm + HD, eps);
     attn_qtile_chunked<HDT, NKT, (HDT <= 3 ? ATTN_CH : 4)>(Ks, Vs, qa, N, scale_log2, lane, ok0 ? obase + q0 * ldo : nullptr,
@@ -1288,11 +1311,13 @@ __global__ __launch_bounds__(512) void attn_fa5_bf16(const bf16_t* __restrict__ 
 // pair, no staging or launch on the critical path except V's DMA behind the k-norm.
 // LDS: 3 x NP16 x HD x 2 B + gamma / beta + 3 x nlast x (HD + 4) x 4 B (N = 260, hd = 96: 163,008 B).
 // ---------------------------------------------------------------------------
-template <int HDT>
+// LIM (sdp_attention_rows, q_rows < N): a compute wave whose query tile lies at or past q_rows
+// skips its tile (and waves 9, 10 the last tile's merge); staging, k-norm and barriers are unchanged.
+template <int HDT, bool LIM = false>
 __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void attn_fa6_bf16(
     const bf16_t* __restrict__ QKV, int64_t ldq, bf16_t* __restrict__ O, int64_t ldo, int B, int N, int H,
     const float* __restrict__ gq, const float* __restrict__ bq, const float* __restrict__ gk,
-    const float* __restrict__ bk, float eps, float scale_log2) {
+    const float* __restrict__ bk, float eps, float scale_log2, int q_rows) {
   extern __shared__ __attribute__((aligned(16))) char sm[];
   constexpr int NKT = 9, HD = 32 * HDT, PP = HD + 4, D4 = HD / 4;
   static_assert(ATTN_CH2 == 3, "the last tile's key ranges are whole chunks of 3 key tiles");
@@ -1382,6 +1407,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void a
   const int q0 = qt * 32 + r;
   const bool ok0 = q0 < N;
   const int64_t off0 = (int64_t)(ok0 ? q0 : N - 1) * ldq;
+  const bool need = LIM ? qt * 32 < q_rows : true;  // wave-uniform
   bf16x8 qa[2 * HDT];
   int ik = 0, iv = 1, is = 2;  // images holding K_j, V_j and the spare
   int pair = pair_of(0), prev = pair;
@@ -1398,7 +1424,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void a
       if (j == 0) barrier();                             // K_0 and gamma / beta visible
     } else {
       if (j == 0) barrier();
-      if (j > 0 && wave >= NKT) merge(prev);
+      if (j > 0 && wave >= NKT && need) merge(prev);
       if (norm && 32 * wave < NP16) attn_knorm32<HDT>(img(ik), 32 * wave, NP16, lane, prm + 2 * HD, prm + 3 * HD, eps);
       SDP_ASTAMP6(j, 1);
     }
@@ -1410,7 +1436,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void a
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       SDP_ASTAMP6(j, 3);
-    } else {
+    } else if (need) {
       // lane-derived values re-made opaque each pair: hoisted out of the loop they stay live
       // through the compute (masks, LDS lane offsets) and push it past 168 VGPRs
       int ln = lane;
@@ -1443,7 +1469,7 @@ __global__ __launch_bounds__(768) __attribute__((amdgpu_waves_per_eu(3))) void a
     prev = pair;
     pair = nxt;
   }
-  if (!producer && wave >= NKT) merge(prev);
+  if (!producer && wave >= NKT && need) merge(prev);
 }
 
 static size_t attn_fa6_bytes(int N, int hd) {
@@ -1454,10 +1480,10 @@ static size_t attn_fa6_bytes(int N, int hd) {
 template <int HDT>
 static int launch_attn_fa6(const void* QKV, int64_t ldq, void* O, int64_t ldo, int B, int N, int H,
                            const float* gq, const float* bq, const float* gk, const float* bk, float eps, float scale,
-                           hipStream_t s) {
+                           int q_rows, hipStream_t s) {
   if (N <= 256 || N > 288) return (int)hipErrorInvalidValue;  // 9 key tiles only
   const size_t bytes = attn_fa6_bytes(N, 32 * HDT);
-  const void* fn = (const void*)attn_fa6_bf16<HDT>;
+  const void* fn = q_rows < N ? (const void*)attn_fa6_bf16<HDT, true> : (const void*)attn_fa6_bf16<HDT, false>;
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   if (e != hipSuccess) return (int)e;
   int dev = 0, ncu = 256;
@@ -1470,7 +1496,7 @@ static int launch_attn_fa6(const void* QKV, int64_t ldq, void* O, int64_t ldo, i
   const bf16_t* q = (const bf16_t*)QKV;
   bf16_t* o = (bf16_t*)O;
   void* args[] = {(void*)&q, (void*)&ldq, (void*)&o, (void*)&ldo, (void*)&B, (void*)&N, (void*)&H, (void*)&gq,
-                  (void*)&bq, (void*)&gk, (void*)&bk, (void*)&eps, (void*)&sl};
+                  (void*)&bq, (void*)&gk, (void*)&bk, (void*)&eps, (void*)&sl, (void*)&q_rows};
   e = hipLaunchKernel(fn, dim3(grid), dim3(768), args, bytes, s);
   if (e != hipSuccess) return (int)e;
   return SDP_CHECK_LAUNCH();
@@ -1665,18 +1691,19 @@ static size_t attn_fa4_bytes(int N, int hd) { return (size_t)2 * ((N + 15) / 16 
 template <int HDT>
 static int launch_attn_fa4(const void* QKV, int64_t ldq, void* O, int64_t ldo, int B, int N, int H,
                            const float* gq, const float* bq, const float* gk, const float* bk, float eps, float scale,
-                           hipStream_t s) {
+                           int q_rows, hipStream_t s) {
   const size_t bytes = attn_fa4_bytes(N, 32 * HDT);
   const void* fn;
+  const bool lim = q_rows < N;
   switch ((N + 31) / 32) {
-    case 1: fn = (const void*)attn_fa4_bf16<HDT, 1>; break;
-    case 2: fn = (const void*)attn_fa4_bf16<HDT, 2>; break;
-    case 3: fn = (const void*)attn_fa4_bf16<HDT, 3>; break;
-    case 4: fn = (const void*)attn_fa4_bf16<HDT, 4>; break;
-    case 5: fn = (const void*)attn_fa4_bf16<HDT, 5>; break;
-    case 6: fn = (const void*)attn_fa4_bf16<HDT, 6>; break;
-    case 7: fn = (const void*)attn_fa4_bf16<HDT, 7>; break;
-    case 8: fn = (const void*)attn_fa4_bf16<HDT, 8>; break;
+    case 1: fn = lim ? (const void*)attn_fa4_bf16<HDT, 1, true> : (const void*)attn_fa4_bf16<HDT, 1>; break;
+    case 2: fn = lim ? (const void*)attn_fa4_bf16<HDT, 2, true> : (const void*)attn_fa4_bf16<HDT, 2>; break;
+    case 3: fn = lim ? (const void*)attn_fa4_bf16<HDT, 3, true> : (const void*)attn_fa4_bf16<HDT, 3>; break;
+    case 4: fn = lim ? (const void*)attn_fa4_bf16<HDT, 4, true> : (const void*)attn_fa4_bf16<HDT, 4>; break;
+    case 5: fn = lim ? (const void*)attn_fa4_bf16<HDT, 5, true> : (const void*)attn_fa4_bf16<HDT, 5>; break;
+    case 6: fn = lim ? (const void*)attn_fa4_bf16<HDT, 6, true> : (const void*)attn_fa4_bf16<HDT, 6>; break;
+    case 7: fn = lim ? (const void*)attn_fa4_bf16<HDT, 7, true> : (const void*)attn_fa4_bf16<HDT, 7>; break;
+    case 8: fn = lim ? (const void*)attn_fa4_bf16<HDT, 8, true> : (const void*)attn_fa4_bf16<HDT, 8>; break;
     default: return (int)hipErrorInvalidValue;
   }
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
@@ -1701,7 +1728,7 @@ static int launch_attn_fa4(const void* QKV, int64_t ldq, void* O, int64_t ldo, i
   const bf16_t* q = (const bf16_t*)QKV;
   bf16_t* o = (bf16_t*)O;
   void* args[] = {(void*)&q, (void*)&ldq, (void*)&o, (void*)&ldo, (void*)&B, (void*)&N, (void*)&H, (void*)&gq,
-                  (void*)&bq, (void*)&gk, (void*)&bk, (void*)&eps, (void*)&sl};
+                  (void*)&bq, (void*)&gk, (void*)&bk, (void*)&eps, (void*)&sl, (void*)&q_rows};
   e = hipLaunchKernel(fn, dim3(grid), dim3(256), args, bytes, s);
   if (e != hipSuccess) return (int)e;
   return SDP_CHECK_LAUNCH();
@@ -1812,10 +1839,36 @@ extern "C" int sdp_attention_variant(int dtype, int N, int n_head, int head_dim,
 int sdp_qk_headnorm(int dtype, void* QKV, int64_t ld, int64_t rows, int n_head, int head_dim, const float* gq,
                     const float* bq, const float* gk, const float* bk, float eps, void* stream);
 
+static int attention_impl(int dtype, const void* QKV, int64_t ldq, void* O, int64_t ldo, int B, int N,
+                          int n_head, int head_dim, const float* q_gamma, const float* q_beta,
+                          const float* k_gamma, const float* k_beta, float eps, const float* mask, int64_t mask_sb,
+                          int64_t mask_sh, int q_rows, void* stream);
+
 extern "C" int sdp_attention(int dtype, const void* QKV, int64_t ldq, void* O, int64_t ldo, int B, int N,
                              int n_head, int head_dim, const float* q_gamma, const float* q_beta,
                              const float* k_gamma, const float* k_beta, float eps, const float* mask, int64_t mask_sb,
                              int64_t mask_sh, void* stream) {
+  return attention_impl(dtype, QKV, ldq, O, ldo, B, N, n_head, head_dim, q_gamma, q_beta, k_gamma, k_beta, eps, mask,
+                        mask_sb, mask_sh, N, stream);
+}
+
+// sdp_attention whose caller reads only output rows [0, q_rows) of every image: those rows equal
+// sdp_attention's bit for bit, rows at or past q_rows may or may not be written.  attn_fa4 and
+// attn_fa6 compute only the query tiles that intersect the range; every other kernel computes all
+// rows.  q_rows >= N is sdp_attention.
+extern "C" int sdp_attention_rows(int dtype, const void* QKV, int64_t ldq, void* O, int64_t ldo, int B, int N,
+                                  int n_head, int head_dim, const float* q_gamma, const float* q_beta,
+                                  const float* k_gamma, const float* k_beta, float eps, const float* mask,
+                                  int64_t mask_sb, int64_t mask_sh, int q_rows, void* stream) {
+  if (q_rows <= 0) return (int)hipErrorInvalidValue;
+  return attention_impl(dtype, QKV, ldq, O, ldo, B, N, n_head, head_dim, q_gamma, q_beta, k_gamma, k_beta, eps, mask,
+                        mask_sb, mask_sh, q_rows < N ? q_rows : N, stream);
+}
+
+static int attention_impl(int dtype, const void* QKV, int64_t ldq, void* O, int64_t ldo, int B, int N,
+                          int n_head, int head_dim, const float* q_gamma, const float* q_beta,
+                          const float* k_gamma, const float* k_beta, float eps, const float* mask, int64_t mask_sb,
+                          int64_t mask_sh, int q_rows, void* stream) {
   if (SDP_DIAG_SKIP(2)) return 0;  // timing experiment, diagnostic build only (misc.hip)
   if (!QKV || !O || B < 0 || N <= 0 || n_head <= 0 || head_dim <= 0 || head_dim > 128)
     return (int)hipErrorInvalidValue;
@@ -1856,20 +1909,20 @@ extern "C" int sdp_attention(int dtype, const void* QKV, int64_t ldq, void* O, i
     const float *gq = norm ? q_gamma : nullptr, *bq = norm ? q_beta : nullptr;
     const float *gk = norm ? k_gamma : nullptr, *bk = norm ? k_beta : nullptr;
     switch (head_dim / 32) {
-      case 1: return launch_attn_fa4<1>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, s);
-      case 2: return launch_attn_fa4<2>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, s);
-      case 3: return launch_attn_fa4<3>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, s);
-      default: return launch_attn_fa4<4>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, s);
+      case 1: return launch_attn_fa4<1>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, q_rows, s);
+      case 2: return launch_attn_fa4<2>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, q_rows, s);
+      case 3: return launch_attn_fa4<3>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, q_rows, s);
+      default: return launch_attn_fa4<4>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, q_rows, s);
     }
   }
   if (variant == 3) {
     const float *gq = norm ? q_gamma : nullptr, *bq = norm ? q_beta : nullptr;
     const float *gk = norm ? k_gamma : nullptr, *bk = norm ? k_beta : nullptr;
     switch (head_dim / 32) {
-      case 1: return launch_attn_fa2<1>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, s);
-      case 2: return launch_attn_fa2<2>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, s);
-      case 3: return launch_attn_fa2<3>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, s);
-      default: return launch_attn_fa2<4>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, s);
+      case 1: return launch_attn_fa2<1>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, q_rows, s);
+      case 2: return launch_attn_fa2<2>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, q_rows, s);
+      case 3: return launch_attn_fa2<3>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, q_rows, s);
+      default: return launch_attn_fa2<4>(QKV, ldq, O, ldo, B, N, n_head, gq, bq, gk, bk, eps, scale, q_rows, s);
     }
   }
   if (variant == 2) {

@@ -43,6 +43,11 @@ def _dense(t: torch.Tensor) -> Rows:
 # A/B switch (benchmarks): SDPNET_LN_FOLD=0 runs the LayerNorms as separate row-LN
 # kernels feeding unfolded GEMMs (the statistics still come from the partials).
 _LN_FOLD = os.environ.get("SDPNET_LN_FOLD", "1") != "0"
+# A/B switch (benchmarks, tests): SDPNET_FINAL_ROWS=0 runs the final encoder on every token row
+# even when only the register rows are read (model.final_rows = False does the same per model).
+_FINAL_ROWS = os.environ.get("SDPNET_FINAL_ROWS", "1") != "0"
+# smallest M the bf16 fast GEMM takes (sdp_gemm_variant); checked where it is used
+_FAST_GEMM_MIN_M = 128
 
 
 def new_partials(rows: int, C: int, device) -> torch.Tensor:
@@ -431,14 +436,34 @@ class EncoderLayer(nn.Module):
             add = add.contiguous()
         return add, add.stride(0), add.stride(1)
 
+    def _rows_limited_ok(self, dt, T: int, M: int, F_: int) -> bool:
+        """The rows-limited mode must send its three GEMMs down the kernel the full-batch
+        call takes (the routes differ in summation order), or it is not taken."""
+        C = self.embedding_dim
+        return all(sp.gemm_variant(dt, M, n, k) == sp.gemm_variant(dt, T, n, k)
+                   for n, k in ((C, C), (F_, C), (C, F_)))
+
     def _run_tokens(self, tok: torch.Tensor, B: int, N: int, dt, mask: Optional[torch.Tensor] = None,
-                    part: Optional[torch.Tensor] = None):
+                    part: Optional[torch.Tensor] = None, lead_rows: int = 0):
         """In place on the dense token buffer ``tok`` [B*N, C] (registers first).
-        ``part``: its LN partial statistics (computed here when not given)."""
+        ``part``: its LN partial statistics (computed here when not given).
+
+        ``lead_rows`` = R > 0 asks for the layer's output on the first R rows of every image
+        only (the final encoder under a register head: nothing else is read).  K and V still
+        come from all rows; attention, o_proj, the FFN and their LN statistics run on the B*R
+        rows, gathered into a dense buffer that is returned ([>= B*R, C], image-major); ``tok``
+        keeps the layer's input.  Per-row arithmetic is that of the full call.  Returns None
+        when the full call ran instead (a mask, or GEMM routes that would differ)."""
         C, Hn, hd = self.embedding_dim, self.n_head, self.head_dim
         T = B * N
         w = self._prep(dt)
         dev = tok.device
+        R = lead_rows
+        M = Mp = B * R
+        if R and M < _FAST_GEMM_MIN_M <= T and dt == torch.bfloat16:
+            Mp = _FAST_GEMM_MIN_M  # zero rows up to the fast GEMM's smallest M
+        if R and (mask is not None or R >= N or not self._rows_limited_ok(dt, T, Mp, w["w1"].shape[0])):
+            R = 0
         if part is None:
             part = new_partials(T, C, dev)
             sp.row_partials(_dense(tok), T, C, part)
@@ -457,8 +482,20 @@ class EncoderLayer(nn.Module):
             mb, sb, sh = self._mask_bias(mask, B, N)
             sp.attention(qkv, att, B, N, Hn, hd, mb, sb, sh, qk_norm=qkn, eps=w.get("qe", 1e-5))  # :289-298
         else:
-            sp.attention(qkv, att, B, N, Hn, hd, qk_norm=qkn, eps=w.get("qe", 1e-5))
-        sp.gemm(_dense(att), w["wo"], _dense(tok), T, C, C, resid=_dense(tok), part=part)  # :300-303
+            sp.attention(qkv, att, B, N, Hn, hd, qk_norm=qkn, eps=w.get("qe", 1e-5), q_rows=R or None)
+        xa = _dense(att)
+        if R:
+            # the B*R rows from here on: a dense copy of tok's, with statistics of its own
+            alloc = torch.zeros if Mp > M else torch.empty
+            lead = alloc(Mp, C, dtype=dt, device=dev)
+            sp.copy_rows(tok, C, N * C, lead, C, R * C, B, R, C)
+            if Mp > M:
+                xa = _dense(alloc(Mp, C, dtype=dt, device=dev))
+                sp.copy_rows(att, C, N * C, xa.t, C, R * C, B, R, C)
+            else:
+                xa = Rows(att, C, R, N, 0)
+            tok, T, part = lead, Mp, new_partials(Mp, C, dev)
+        sp.gemm(xa, w["wo"], _dense(tok), T, C, C, resid=_dense(tok), part=part)  # :300-303
         # LN2 (:307) folded into ff_linear1 (:308)
         F_ = w["w1"].shape[0]
         f = torch.empty(T, F_, dtype=dt, device=dev)
@@ -471,6 +508,7 @@ class EncoderLayer(nn.Module):
             sp.layernorm(_dense(tok), w["n2g"], w["n2b"], w["n2e"], _dense(h), T, C)
             sp.gemm(_dense(h), w["w1"], _dense(f), T, F_, C, bias=w["c1"], act=act_code(self.activation))
         sp.gemm(_dense(f), w["w2"], _dense(tok), T, C, F_, bias=w["b2"], resid=_dense(tok), part=part)  # :308-309
+        return tok if R else None
 
     def forward(self, x: torch.Tensor, register: torch.Tensor, mask: torch.Tensor = None):
         if self.training:
@@ -570,8 +608,12 @@ class FinalBlock(nn.Module):
                                     multiplication_factor=multiplication_factor, ff_dropout=ff_dropout,
                                     att_dropout=att_dropout, normalize_qv=normalize_qv, drop_p=drop_p)
 
-    def _run_tokens(self, tok, B, R, H, W, dt, mask=None, part: Optional[torch.Tensor] = None):
-        self.t_block._run_tokens(tok, B, R + H * W, dt, mask, part=part)
+    def _run_tokens(self, tok, B, R, H, W, dt, mask=None, part: Optional[torch.Tensor] = None,
+                    registers_only: bool = False):
+        """``registers_only``: the caller reads the register rows alone; returns them as a dense
+        [>= B*R, C] buffer (EncoderLayer._run_tokens, lead_rows) or None after the full run."""
+        return self.t_block._run_tokens(tok, B, R + H * W, dt, mask, part=part,
+                                        lead_rows=R if registers_only else 0)
 
     def forward(self, x: torch.Tensor, register: torch.Tensor, mask: torch.Tensor = None):
         return self.t_block(x, register, mask)

@@ -27,6 +27,7 @@ from numpy import arccos, cos
 
 import sdpnet_hip as sp
 import sdpnet_ops
+import layers
 from layers import ConvMixer, EmbeddingLayer, ConvPatcher, Block, FinalBlock, ClassificationHead, ConvEmbedding  # noqa: F401
 from utility_layers import SdPModel, StochasticDepth  # noqa: F401
 from layers import new_partials  # token-buffer plumbing of the fused path
@@ -255,8 +256,16 @@ class MainModel(SdPModel):
             sp.row_partials(Rows(tok, C, R, N, 0), B * R, C, part)
         for block in self.blocks:                                     # model.py:139-140
             block._run_tokens(tok, B, R, Hp, Wp, dt, part=part)
-        self.final_block._run_tokens(tok, B, R, Hp, Wp, dt, part=part)  # model.py:143
         head = self.output_head                                       # model.py:146
+        # logits from the registers alone: the final encoder's image rows are never read, so it
+        # computes K / V for them and everything after attention on the register rows only
+        on = getattr(self, "final_rows", None)
+        regs_only = (head.from_register and not return_raw_outputs and R > 0
+                     and bool(layers._FINAL_ROWS if on is None else on))
+        lead = self.final_block._run_tokens(tok, B, R, Hp, Wp, dt, part=part, registers_only=regs_only)  # model.py:143
+        if lead is not None:
+            head._run(Rows(lead, C), B, R, C, dt, out=logits)
+            return None
         if head.from_register:
             head._run(Rows(tok, C, R, N, 0), B, R, C, dt, out=logits)
         else:

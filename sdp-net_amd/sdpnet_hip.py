@@ -62,6 +62,8 @@ _SIGS = {
     "sdp_dwconv_set_kernel": ([_i32], _i32),
     "sdp_attention": ([_i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i64,
                        _i64, _vp], _i32),
+    "sdp_attention_rows": ([_i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i64,
+                            _i64, _i32, _vp], _i32),
     "sdp_attention_variant": ([_i32, _i32, _i32, _i32, _i32], _i32),
     "sdp_attention_set_kernel": ([_i32], _i32),
     "sdp_patchify": ([_i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp], _i32),
@@ -367,15 +369,23 @@ def dwconv(x: Rows, weight: torch.Tensor, bias: Optional[torch.Tensor], y: Rows,
 
 def attention(qkv: torch.Tensor, out: torch.Tensor, B: int, N: int, n_head: int, head_dim: int,
               mask: Optional[torch.Tensor] = None, mask_sb: int = 0, mask_sh: int = 0, qk_norm=None,
-              eps: float = 1e-5):
+              eps: float = 1e-5, q_rows: Optional[int] = None):
     """qk_norm = (q_gamma, q_beta, k_gamma, k_beta) fp32 or None.  NOTE: when the
-    generic kernel is taken the norms are applied in place on ``qkv``."""
+    generic kernel is taken the norms are applied in place on ``qkv``.
+    q_rows: the caller reads only output rows [0, q_rows) of every image
+    (sdp_attention_rows): the rest of ``out`` may be left unwritten."""
     _need_cuda(qkv, out, mask)
     _req(qkv.dtype == out.dtype)
     gq, bq, gk, bk = qk_norm if qk_norm is not None else (None, None, None, None)
-    rc = lib().sdp_attention(dcode(qkv.dtype), qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), B, N,
-                             n_head, head_dim, _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk), float(eps), _ptr(mask),
-                             mask_sb, mask_sh, _stream(out))
+    if q_rows is None:
+        rc = lib().sdp_attention(dcode(qkv.dtype), qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), B,
+                                 N, n_head, head_dim, _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk), float(eps), _ptr(mask),
+                                 mask_sb, mask_sh, _stream(out))
+    else:
+        _req(q_rows >= 1)
+        rc = lib().sdp_attention_rows(dcode(qkv.dtype), qkv.data_ptr(), qkv.stride(0), out.data_ptr(),
+                                      out.stride(0), B, N, n_head, head_dim, _ptr(gq), _ptr(bq), _ptr(gk), _ptr(bk),
+                                      float(eps), _ptr(mask), mask_sb, mask_sh, int(q_rows), _stream(out))
     _check(rc, "attention")
 
 
