@@ -556,6 +556,36 @@ int sdp_bce_loss(int dtype, const void* logits, int64_t ldl, const int64_t* labe
 int sdp_bce_loss_soft(int dtype, const void* logits, int64_t ldl, const float* targets, int64_t ldt, int B, int K,
                       float eps, float grad_scale, void* dlogits, int64_t ldd, float* loss, void* stream);
 
+/* Knowledge distillation, base loss and teacher term in one launch (the reference's Trainer stores
+ * its teacher_model and never calls it, training_tools.py:64, so this arithmetic is this
+ * package's): student logits z [B][ldl] (dtype), teacher logits t [B][ldt] (tdtype; fp32 or bf16,
+ * each independently), and exactly one of labels (int64 [B]) / targets (fp32 rows [B][ldy]).
+ *   loss = (1 - alpha) Base(z, y) + alpha Distill(z, t),  alpha in [0, 1]
+ *   Base: mode bit0 = 0 the cross entropy of sdp_ce_loss / sdp_ce_loss_soft (mean over B rows; no
+ *     ignore_index here), bit0 = 1 the binary cross entropy of sdp_bce_loss / sdp_bce_loss_soft
+ *     (mean over B K elements), on t' = (1 - eps) y + eps / K.
+ *   Distill: mode bit1 = 0 (soft), Hinton's T^2 / B * sum_i KL(softmax(t_i / T) || softmax(z_i / T))
+ *     (torch's kl_div(..., reduction="batchmean") times T^2), evaluated as
+ *     T^2 [sum_k q_k (t_k - z_k) / T - lse(t / T) + lse(z / T)], q = softmax(t / T), so that a
+ *     teacher probability that underflows to 0 adds 0; bit1 = 1 (hard), 1 / B * sum_i -log
+ *     softmax(z_i)[a_i] with a_i the lowest index of the maximum of the stored t_i (no smoothing,
+ *     temperature unused).
+ *   dlogits_i = grad_scale ((1 - alpha) Base'_i + alpha T / B (softmax(z_i / T) - softmax(t_i / T)))  (soft)
+ *             = grad_scale ((1 - alpha) Base'_i + alpha / B (softmax(z_i) - onehot(a_i)))             (hard)
+ *     in the student's dtype (may be NULL), Base' the base kernels' gradient per unit grad_scale.
+ *     The teacher gets no gradient.
+ * All arithmetic is fp32 with the row maxima subtracted before every exp.  *loss += loss (one
+ * atomic per row); parts (may be NULL): parts[0] += Base, parts[1] += Distill, both unweighted,
+ * T^2 included, so loss = (1 - alpha) parts[0] + alpha parts[1].  A hard label outside [0, K)
+ * makes its row's loss and gradient NaN and is never used as an index.  Returns
+ * hipErrorInvalidValue, before any launch, for a null logits / teacher / loss, both or neither of
+ * labels / targets, B < 0, K <= 0, alpha outside [0, 1], a temperature that is not a finite
+ * positive number, mode outside 0..3 or an unknown dtype; B == 0 is a no-op. */
+int sdp_distill_loss(int dtype, const void* logits, int64_t ldl, int tdtype, const void* teacher, int64_t ldt,
+                     const int64_t* labels, const float* targets, int64_t ldy, int B, int K, float eps, float alpha,
+                     float temperature, int mode, float grad_scale, void* dlogits, int64_t ldd, float* loss,
+                     float* parts, void* stream);
+
 /* Multi-tensor weight average (EMA_model.update_parameters, training_tools.py:291-297) over the
  * block table of sdp_adamw: out[t][i] = fl(fl(d * a[t][i]) + fl(c * b[t][i])), three fp32
  * roundings and no FMA, so the result is bit-identical to torch's `d * e + c * w`.  A running

@@ -2341,6 +2341,179 @@ extern "C" int sdp_bce_loss_soft(int dtype, const void* logits, int64_t ldl, con
 }
 
 // ---------------------------------------------------------------------------
+// Knowledge distillation: loss = (1 - alpha) Base(z, y) + alpha Distill(z, t), student logits z,
+// teacher logits t (either fp32 or bf16, independently), y hard labels or fp32 target rows.
+//   Base     the arithmetic of ce_k (mode bit0 = 0; mean over B rows, no ignore_index) or bce_k
+//            (bit0 = 1; mean over B K elements) on t' = (1 - eps) y + eps / K
+//   Distill  soft (bit1 = 0): T^2 / B * sum_i KL(softmax(t_i / T) || softmax(z_i / T)), with both row
+//              maxima taken out so that they cancel exactly:
+//              KL_i = sum_k e_k ((t_k - mt) - (z_k - mz)) / (T S_t) - log S_t + log S_z,
+//              e_k = exp((t_k - mt) / T), S_t = sum e, S_z = sum exp((z_k - mz) / T); a term with
+//              e_k = 0 adds 0
+//            hard (bit1 = 1): 1 / B * sum_i (lse(z_i) - z_i[a_i]), a_i the lowest index of the
+//              maximum of t_i; no smoothing, no temperature
+//   dlogits_i = grad_scale * ((1 - alpha) Base'_i + alpha T / B (softmax(z_i / T) - softmax(t_i / T)))  soft
+//             = grad_scale * ((1 - alpha) Base'_i + alpha / B (softmax(z_i) - onehot(a_i)))            hard
+// One wave per row; the rows are read from HBM in the first pass and from cache after it.  One
+// atomic per row into *loss, and one each into parts[0] (Base) and parts[1] (Distill, T^2
+// included), both unweighted.  A hard label outside [0, K) is only compared with the column
+// index: its row's loss and gradient are NaN.
+// ---------------------------------------------------------------------------
+template <typename T, typename TT, bool SOFT>
+__global__ __launch_bounds__(256) void distill_k(const T* __restrict__ L, int64_t ldl, const TT* __restrict__ Tc,
+                                                 int64_t ldt, const int64_t* __restrict__ y,
+                                                 const float* __restrict__ tg, int64_t ldy, int B, int K, float eps,
+                                                 float alpha, float temp, int mode, float grad_scale,
+                                                 T* __restrict__ D, int64_t ldd, float* __restrict__ loss,
+                                                 float* __restrict__ parts) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= B) return;
+  const bool bce = mode & 1, hard = mode & 2;
+  const T* lp = L + r * ldl;
+  const TT* tp = Tc + r * ldt;
+  const float* yp = SOFT ? tg + r * ldy : nullptr;
+  int64_t lab = 0;
+  float bad = 0.0f;
+  if constexpr (!SOFT) {
+    lab = y[r];
+    if (!(lab >= 0 && lab < K)) bad = NAN;
+  }
+  const float on = 1.0f - eps, off = eps / (float)K, invT = 1.0f / temp;
+  // pass 1: row maxima, the teacher's first argmax, sum of z (hard-label CE smoothing term)
+  float mz = -INFINITY, sl = 0.f, mt = -INFINITY;
+  int am = INT_MAX;
+  for (int c = lane; c < K; c += 64) {
+    const float z = to_f<T>(lp[c]), t = to_f<TT>(tp[c]);
+    mz = fmaxf(mz, z);
+    sl += z;
+    if (t > mt) {  // ascending c: the lowest index of this lane's maximum
+      mt = t;
+      am = c;
+    }
+  }
+  mz = wave_max(mz);
+  sl = wave_sum(sl);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(mt, o, 64);
+    const int oi = __shfl_xor(am, o, 64);
+    if (ov > mt || (ov == mt && oi < am)) {
+      mt = ov;
+      am = oi;
+    }
+  }
+  if (am >= K) am = 0;  // a row with no value above -inf: stay inside the row
+  // pass 2: the exp sums and the base loss
+  float se = 0.f, seT = 0.f, stT = 0.f, acc = 0.f, st = 0.f, stl = 0.f, sb = 0.f;
+  for (int c = lane; c < K; c += 64) {
+    const float z = to_f<T>(lp[c]), dz = z - mz;
+    if (!bce || hard) se += expf(dz);
+    if (!hard) {
+      const float dt = to_f<TT>(tp[c]) - mt, et = expf(dt * invT);
+      seT += expf(dz * invT);
+      stT += et;
+      if (et > 0.f) acc = fmaf(et, dt - dz, acc);
+    }
+    float yv;
+    if constexpr (SOFT) yv = fmaf(on, yp[c], off);
+    else yv = (c == lab ? on : 0.0f) + off;
+    if (bce) {
+      const float m = fmaxf(-z, 0.f);
+      sb += (1.0f - yv) * z + m + logf(expf(-m) + expf(-z - m));
+    } else if constexpr (SOFT) {
+      st += yv;
+      stl = fmaf(yv, z, stl);
+    }
+  }
+  se = wave_sum(se);
+  seT = wave_sum(seT);
+  stT = wave_sum(stT);
+  acc = wave_sum(acc);
+  st = wave_sum(st);
+  stl = wave_sum(stl);
+  sb = wave_sum(sb);
+  const float nrows = (float)B, inv_n = 1.0f / ((float)B * (float)K);
+  const float lse = mz + logf(se);
+  float base, tsum = 1.0f;
+  if (bce) {
+    base = sb * inv_n + bad;
+  } else if constexpr (SOFT) {
+    tsum = st;
+    base = (lse * st - stl) / nrows;
+  } else {
+    const float ly = (bad == 0.0f) ? to_f<T>(lp[lab]) : NAN;
+    base = ((1.0f - eps) * (lse - ly) + eps * (lse - sl / (float)K)) / nrows;
+  }
+  float dist;
+  if (hard) dist = (lse - to_f<T>(lp[am])) / nrows;
+  else dist = temp * temp * (acc * invT / stT + (logf(seT) - logf(stT))) / nrows;
+  if (lane == 0) {
+    atomicAdd(loss, (1.0f - alpha) * base + alpha * dist);
+    if (parts) {
+      atomicAdd(parts, base);
+      atomicAdd(parts + 1, dist);
+    }
+  }
+  if (!D) return;
+  const float sc = grad_scale / nrows, scb = grad_scale * inv_n, wb = 1.0f - alpha;
+  const float inv = 1.0f / se, invz = 1.0f / seT, invt = 1.0f / stT;
+  for (int c = lane; c < K; c += 64) {
+    const float z = to_f<T>(lp[c]), dz = z - mz;
+    float yv;
+    if constexpr (SOFT) yv = fmaf(on, yp[c], off);
+    else yv = (c == lab ? on : 0.0f) + off;
+    float bg, dg;
+    if (bce) bg = scb * (1.0f / (1.0f + expf(-z)) - yv) + bad;
+    else bg = sc * (expf(dz) * inv * tsum - yv) + bad;
+    if (hard) dg = sc * (expf(dz) * inv - (c == am ? 1.0f : 0.0f));
+    else dg = sc * temp * (expf(dz * invT) * invz - expf((to_f<TT>(tp[c]) - mt) * invT) * invt);
+    D[r * ldd + c] = from_f<T>(wb * bg + alpha * dg);
+  }
+}
+
+template <typename T, typename TT>
+static void distill_launch(const void* logits, int64_t ldl, const void* teacher, int64_t ldt, const int64_t* labels,
+                           const float* targets, int64_t ldy, int B, int K, float eps, float alpha, float temp,
+                           int mode, float grad_scale, void* dlogits, int64_t ldd, float* loss, float* parts,
+                           hipStream_t s) {
+  dim3 grid((B + 3) / 4);
+  if (targets)
+    hipLaunchKernelGGL((distill_k<T, TT, true>), grid, dim3(256), 0, s, (const T*)logits, ldl, (const TT*)teacher, ldt,
+                       labels, targets, ldy, B, K, eps, alpha, temp, mode, grad_scale, (T*)dlogits, ldd, loss, parts);
+  else
+    hipLaunchKernelGGL((distill_k<T, TT, false>), grid, dim3(256), 0, s, (const T*)logits, ldl, (const TT*)teacher,
+                       ldt, labels, targets, ldy, B, K, eps, alpha, temp, mode, grad_scale, (T*)dlogits, ldd, loss,
+                       parts);
+}
+
+extern "C" int sdp_distill_loss(int dtype, const void* logits, int64_t ldl, int tdtype, const void* teacher,
+                                int64_t ldt, const int64_t* labels, const float* targets, int64_t ldy, int B, int K,
+                                float eps, float alpha, float temperature, int mode, float grad_scale, void* dlogits,
+                                int64_t ldd, float* loss, float* parts, void* stream) {
+  if (!logits || !teacher || !loss || B < 0 || K <= 0) return (int)hipErrorInvalidValue;
+  if ((labels != nullptr) == (targets != nullptr)) return (int)hipErrorInvalidValue;
+  if (!(alpha >= 0.0f && alpha <= 1.0f) || !(temperature > 0.0f && temperature < INFINITY))
+    return (int)hipErrorInvalidValue;
+  if (mode < 0 || mode > 3 || (dtype != 0 && dtype != 1) || (tdtype != 0 && tdtype != 1))
+    return (int)hipErrorInvalidValue;
+  if (B == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+#define SDP_DISTILL(TZ, TT)                                                                                        \
+  distill_launch<TZ, TT>(logits, ldl, teacher, ldt, labels, targets, ldy, B, K, eps, alpha, temperature, mode,     \
+                         grad_scale, dlogits, ldd, loss, parts, s)
+  if (dtype == 1) {
+    if (tdtype == 1) SDP_DISTILL(bf16_t, bf16_t);
+    else SDP_DISTILL(bf16_t, float);
+  } else {
+    if (tdtype == 1) SDP_DISTILL(float, bf16_t);
+    else SDP_DISTILL(float, float);
+  }
+#undef SDP_DISTILL
+  return SDP_CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------------------
 // Multi-tensor gradient norm and AdamW.  Tensors are fp32; the work list is a table of
 // (tensor, first element) per 4096-element block built once by the host.
 //   sdp_grad_sumsq: state[0] += sum g^2 over every tensor, state[1] = 1 if any g is non-finite

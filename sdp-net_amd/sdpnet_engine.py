@@ -71,7 +71,8 @@ def act_code(fn: Callable) -> int:
 
 
 def _key(params, dtype, device):
-    return (dtype, str(device)) + tuple((p._version, p.data_ptr()) for p in params)
+    # a tensor made under torch.inference_mode() (TeacherModel.forward) has no version counter
+    return (dtype, str(device)) + tuple((-1 if p.is_inference() else p._version, p.data_ptr()) for p in params)
 
 
 def cached(module: nn.Module, name: str, params, dtype: torch.dtype, build: Callable[[], Dict]):

@@ -128,6 +128,8 @@ _SIGS = {
     "sdp_ce_loss_soft": ([_i32, _vp, _i64, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _i64, _vp, _vp], _i32),
     "sdp_bce_loss": ([_i32, _vp, _i64, _vp, _i32, _i32, _f32, _f32, _vp, _i64, _vp, _vp], _i32),
     "sdp_bce_loss_soft": ([_i32, _vp, _i64, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _i64, _vp, _vp], _i32),
+    "sdp_distill_loss": ([_i32, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _f32, _i32, _f32,
+                          _vp, _i64, _vp, _vp, _vp], _i32),
     "sdp_ema_update": ([_vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _vp], _i32),
     "sdp_mt_block_bytes": ([], _i32),
     "sdp_grad_sumsq": ([_vp, _vp, _vp, _i32, _vp, _vp], _i32),
@@ -1015,6 +1017,59 @@ def bce_loss_soft(logits: torch.Tensor, targets: torch.Tensor, eps: float, grad_
                                  targets.stride(0), B, K, float(eps), float(grad_scale), _ptr(dlogits),
                                  dlogits.stride(0) if dlogits is not None else 0, loss.data_ptr(), _stream(loss))
     _check(rc, "bce_loss_soft")
+
+
+def _rows_in_storage(t: torch.Tensor, B: int, K: int) -> bool:
+    """[B, K] rows of unit column stride whose last element lies inside the tensor's storage."""
+    if t.dim() != 2 or tuple(t.shape) != (B, K) or t.stride(1) != 1 or t.stride(0) < 0:
+        return False
+    if B > 1 and t.stride(0) < K:
+        return False
+    last = t.storage_offset() + (B - 1) * t.stride(0) + K - 1
+    return B == 0 or last < t.untyped_storage().nbytes() // t.element_size()
+
+
+DISTILL_BCE, DISTILL_HARD = 1, 2  # sdp_distill_loss mode bits
+
+
+def distill_loss(logits: torch.Tensor, teacher: torch.Tensor, targets: torch.Tensor, eps: float, alpha: float,
+                 temperature: float, mode: int, grad_scale: float, dlogits: Optional[torch.Tensor],
+                 loss: torch.Tensor, parts: Optional[torch.Tensor] = None):
+    """loss[0] += (1 - alpha) Base + alpha Distill in one launch (sdp_distill_loss): the CE (mode
+    bit0 = 0) or BCE (DISTILL_BCE) base on ``targets`` (int64 class indices [B] or fp32 rows [B, K])
+    plus the soft (T^2 KL at ``temperature``) or hard (DISTILL_HARD, the teacher's argmax) teacher
+    term.  ``logits`` and ``teacher`` are fp32 or bf16 [B, K], each on its own; ``dlogits`` like
+    ``logits`` or None; ``parts`` (fp32, 2 elements, optional) accumulates the unweighted terms."""
+    _need_cuda(logits, teacher, targets, dlogits, loss, parts)
+    _req(logits.dim() == 2, "distill_loss: [B, K] logits")
+    B, K = logits.shape
+    _req(K > 0 and _rows_in_storage(logits, B, K), "distill_loss: row-major [B, K] logits")
+    _req(_rows_in_storage(teacher, B, K), "distill_loss: teacher logits shaped like the student's")
+    _req(loss.dtype == torch.float32 and loss.numel() >= 1, "distill_loss: fp32 loss")
+    _req(parts is None or (parts.dtype == torch.float32 and parts.numel() >= 2 and parts.is_contiguous()),
+         "distill_loss: fp32 parts[2]")
+    _req(dlogits is None or (dlogits.dtype == logits.dtype and _rows_in_storage(dlogits, B, K)),
+         "distill_loss: dlogits like logits")
+    _req(0.0 <= float(alpha) <= 1.0, "distill_loss: alpha in [0, 1]")
+    _req(0.0 < float(temperature) < float("inf"), "distill_loss: temperature > 0")
+    _req(int(mode) in (0, 1, 2, 3), "distill_loss: mode in 0..3")
+    lab = tgt = None
+    ldy = 0
+    if targets.dtype == torch.int64:
+        _req(targets.dim() == 1 and targets.numel() == B, "distill_loss: one label per row")
+        targets = targets.contiguous()
+        lab = targets.data_ptr()
+    else:
+        _req(targets.dtype == torch.float32 and _rows_in_storage(targets, B, K), "distill_loss: fp32 [B, K] targets")
+        tgt, ldy = targets.data_ptr(), targets.stride(0)
+    if B == 0:
+        return
+    rc = lib().sdp_distill_loss(dcode(logits.dtype), logits.data_ptr(), logits.stride(0), dcode(teacher.dtype),
+                                teacher.data_ptr(), teacher.stride(0), lab, tgt, ldy, B, K, float(eps), float(alpha),
+                                float(temperature), int(mode), float(grad_scale), _ptr(dlogits),
+                                dlogits.stride(0) if dlogits is not None else 0, loss.data_ptr(), _ptr(parts),
+                                _stream(loss))
+    _check(rc, "distill_loss")
 
 
 def mt_block_table(numels, dev: torch.device) -> Tuple[torch.Tensor, int]:

@@ -1624,6 +1624,78 @@ def bce_with_logits(logits: torch.Tensor, targets: torch.Tensor, label_smoothing
     return _BCEFn.apply(logits, targets, float(label_smoothing))
 
 
+class _DistillFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, teacher, targets, eps, alpha, temperature, mode):
+        out = torch.zeros(3, dtype=torch.float32, device=logits.device)  # loss, Base, Distill
+        logits = logits.contiguous()
+        d = torch.empty_like(logits)
+        if targets.is_floating_point():
+            targets = targets.float().contiguous()
+        parts = out[1:]
+        sp.distill_loss(logits, teacher.contiguous(), targets, eps, alpha, temperature, mode, 1.0, d, out[:1], parts)
+        ctx.save_for_backward(d)  # never the teacher's logits: they may be inference tensors
+        ctx.mark_non_differentiable(parts)
+        return out[0], parts
+
+    @staticmethod
+    def backward(ctx, g, _gparts):
+        (d,) = ctx.saved_tensors
+        out = torch.empty_like(d)
+        M, K = d.shape
+        sc = g.float().reshape(1).expand(M).contiguous()
+        sp.rowscale_add(_dense(d), _dense(out), M, K, scale=sc, sgrp=1)
+        return out, None, None, None, None, None, None
+
+
+def distillation_loss(logits: torch.Tensor, teacher_logits: torch.Tensor, targets: torch.Tensor, *,
+                      alpha: float = 0.5, temperature: float = 1.0, kind: str = "soft", base: str = "ce",
+                      label_smoothing: float = 0.0, num_classes: Optional[int] = None, return_parts: bool = False):
+    """Knowledge distillation as one HIP kernel that also writes dlogits (sdp_distill_loss):
+
+        (1 - alpha) * Base(logits, targets) + alpha * Distill(logits, teacher_logits)
+
+    ``Base`` is ``cross_entropy`` (``base="ce"``, without ignore_index) or ``bce_with_logits``
+    (``"bce"``) with ``label_smoothing``, on int64 class indices [B] or float rows [B, K].
+    ``Distill`` is, for ``kind="soft"``, ``temperature**2 * kl_div(log_softmax(logits / T),
+    softmax(teacher_logits / T), reduction="batchmean")`` and, for ``"hard"``, the unsmoothed cross
+    entropy against the teacher's argmax (lowest index on ties).  ``logits`` and
+    ``teacher_logits`` are fp32 or bf16 [B, K], each on its own.  The teacher receives no gradient
+    and is not kept for backward, so logits made under ``torch.inference_mode()`` are fine.
+    ``return_parts=True`` returns ``(loss, parts)`` with ``parts`` the detached device tensor
+    ``[Base, Distill]`` (unweighted).  ``num_classes``, when given, must be K."""
+    if logits.dim() != 2:
+        raise ValueError(f"distillation_loss takes [B, K] logits, got {tuple(logits.shape)}")
+    K = logits.shape[1]
+    if num_classes is not None and int(num_classes) != K:
+        raise ValueError(f"distillation_loss: logits have {K} classes, num_classes is {num_classes}")
+    if teacher_logits.shape != logits.shape:
+        raise ValueError(f"distillation_loss: teacher logits {tuple(teacher_logits.shape)} for student logits "
+                         f"{tuple(logits.shape)}")
+    for name, t in (("logits", logits), ("teacher_logits", teacher_logits)):
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"distillation_loss: {name} are float32 or bfloat16, got {t.dtype}")
+    if targets.is_floating_point():
+        if targets.shape != logits.shape:
+            raise ValueError(f"distillation_loss: float targets {tuple(targets.shape)} for logits "
+                             f"{tuple(logits.shape)}")
+    elif targets.dtype != torch.int64 or targets.dim() != 1 or targets.shape[0] != logits.shape[0]:
+        raise ValueError("distillation_loss: targets are int64 class indices [B] or float rows [B, K]")
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError(f"distillation_loss: alpha must lie in [0, 1], got {alpha}")
+    if not 0.0 < float(temperature) < float("inf"):
+        raise ValueError(f"distillation_loss: temperature must be positive and finite, got {temperature}")
+    if kind not in ("soft", "hard"):
+        raise ValueError(f"distillation_loss: kind is 'soft' or 'hard', got {kind!r}")
+    if base not in ("ce", "bce"):
+        raise ValueError(f"distillation_loss: base is 'ce' or 'bce', got {base!r}")
+    sp._need_cuda(logits, teacher_logits, targets)
+    mode = (sp.DISTILL_BCE if base == "bce" else 0) | (sp.DISTILL_HARD if kind == "hard" else 0)
+    loss, parts = _DistillFn.apply(logits, teacher_logits, targets, float(label_smoothing), float(alpha),
+                                   float(temperature), mode)
+    return (loss, parts) if return_parts else loss
+
+
 class EMA:
     """The weight average of the reference's ``EMA_model`` (training_tools.py:282-302) with every
     fp32 entry of the state dict updated by ONE multi-tensor HIP launch (``sdp_ema_update``)

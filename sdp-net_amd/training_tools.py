@@ -25,6 +25,11 @@ mirrors the reference (``reference_quirks=True``):
 
 ``Trainer(..., reference_quirks=False)`` gives a true exponential average and zeroes the gradients
 only after a batch on which the optimizer stepped.
+
+The reference stores ``teacher_model`` and never calls it (:64), and so does this Trainer by default
+(``distill_kind="none"``).  ``distill_kind="soft"`` / ``"hard"`` distils from it: the loss becomes
+``sdpnet_train.distillation_loss`` -- (1 - distill_alpha) * the loss above + distill_alpha * the
+teacher term, one kernel -- against the logits of a frozen teacher run once per micro-batch.
 """
 from __future__ import annotations
 
@@ -64,6 +69,9 @@ class Trainer:
         teacher_model: Any = None,
         label_smoothing: float = 0.1,
         reference_quirks: bool = True,
+        distill_kind: str = "none",
+        distill_alpha: float = 0.5,
+        distill_temperature: float = 1.0,
     ) -> None:
         self.gpu_id = gpu_id
         self.reference_quirks = bool(reference_quirks)
@@ -96,7 +104,28 @@ class Trainer:
         self.val_loss_logger = val_loss_logger
         self.train_loss_logger = train_loss_logger
         self.val_accuracy_logger = val_accuracy_logger
-        self.teacher_model = teacher_model  # stored and unused, as in the reference
+        # "none": stored and never called, as in the reference.  "soft" / "hard": the loss becomes
+        # sdpnet_train.distillation_loss against the teacher's logits (see _run_batch)
+        if distill_kind not in ("none", "soft", "hard"):
+            raise ValueError(f"distill_kind is 'none', 'soft' or 'hard', got {distill_kind!r}")
+        self.distill_kind = distill_kind
+        self.distill_alpha = float(distill_alpha)
+        self.distill_temperature = float(distill_temperature)
+        self.distill_parts = None  # [Base, Distill] of the last batch, unweighted, on the device
+        if distill_kind != "none":
+            if teacher_model is None:
+                raise ValueError(f"distill_kind={distill_kind!r} needs a teacher_model")
+            if not callable(teacher_model):
+                raise ValueError("teacher_model must be a TeacherModel, an nn.Module or a callable")
+            if not 0.0 <= self.distill_alpha <= 1.0:
+                raise ValueError(f"distill_alpha must lie in [0, 1], got {distill_alpha}")
+            if not 0.0 < self.distill_temperature < float("inf"):
+                raise ValueError(f"distill_temperature must be positive and finite, got {distill_temperature}")
+            # the teacher is frozen and stays outside DDP, torch.compile, the checkpoint and the EMA
+            net = teacher_model.model if isinstance(teacher_model, TeacherModel) else teacher_model
+            if isinstance(net, nn.Module):
+                net.to(gpu_id).eval().requires_grad_(False)
+        self.teacher_model = teacher_model
         #  Mixed precision training
         self.autocast = torch.autocast
         self.fused = isinstance(optimizer, sdpnet_train.AdamW)
@@ -109,6 +138,7 @@ class Trainer:
             print(f"There is a problem with loading the model weights and the problem is: {e}")
         ## loss_fn
         self.label_smoothing = label_smoothing
+        self.distill_base = "ce" if use_cross_entropy else "bce"
         if use_cross_entropy:
             self.loss_fn = lambda out, tgt: sdpnet_train.cross_entropy(out, tgt, label_smoothing)
         else:
@@ -123,7 +153,18 @@ class Trainer:
 
         with self.autocast(device_type="cuda", dtype=torch.bfloat16):
             output = self.model(source)
-            loss = self.loss_fn(output, targets)
+            if self.distill_kind == "none":
+                loss = self.loss_fn(output, targets)
+            else:
+                with torch.no_grad():
+                    teacher_out = self.teacher_model(source)
+                if not isinstance(teacher_out, torch.Tensor) or teacher_out.shape != output.shape:
+                    got = tuple(teacher_out.shape) if isinstance(teacher_out, torch.Tensor) else type(teacher_out)
+                    raise ValueError(f"the teacher returned {got}, the student's logits are {tuple(output.shape)}")
+                loss, self.distill_parts = sdpnet_train.distillation_loss(
+                    output, teacher_out, targets, alpha=self.distill_alpha, temperature=self.distill_temperature,
+                    kind=self.distill_kind, base=self.distill_base, label_smoothing=self.label_smoothing,
+                    return_parts=True)
 
         if self.fused:
             self.optimizer.scale(loss).backward()
@@ -295,6 +336,30 @@ class TeacherModel:
 
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         return self.forward(x)
+
+    @classmethod
+    def from_checkpoint(cls, path: str, device="cuda", compile_model: bool = False,
+                        config_from: str = None) -> "TeacherModel":
+        """A frozen teacher from a file of this package (``eval_harness.return_model``): a Trainer
+        checkpoint (``Trainer._save_checkpoint``; the model is rebuilt from its ``model_config``),
+        or an EMA file (``EMA_model.save_ema_model``), which is a plain state dict: its
+        ``model_config`` is read from the Trainer checkpoint ``config_from`` (default: ``model.pt``
+        in the same folder)."""
+        import eval_harness
+
+        path = os.path.abspath(path)
+        head = torch.load(path, map_location="cpu", weights_only=True)
+        if isinstance(head, dict) and "model_config" in head and "model_state_dict" in head:
+            model, _ = eval_harness.return_model("", path, None)
+        else:
+            ckpt = os.path.abspath(config_from) if config_from else os.path.join(os.path.dirname(path), "model.pt")
+            if not os.path.exists(ckpt):
+                raise FileNotFoundError(f"{path} holds weights only; the Trainer checkpoint {ckpt} that would give "
+                                        "its model_config is missing (pass config_from)")
+            _, model = eval_harness.return_model("", ckpt, path)
+        del head
+        model = model.to(device).eval().requires_grad_(False)
+        return cls(model, compile_model=compile_model)
 
 
 class EMA_model(sdpnet_train.EMA):
