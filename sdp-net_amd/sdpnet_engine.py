@@ -5,8 +5,10 @@
   is autocast, training_tools.py:85); fp32 otherwise.
 * activation callables -> epilogue codes (model.py:13-24 registry, KeLu).
 * per-module prepared-weight caches (bf16 casts, fused Wqkv, padded patch
-  weight), keyed on the parameters' version counters so load_state_dict /
-  optimizer steps invalidate them.  Not part of the state_dict.
+  weight), keyed on the parameters' version counters and addresses so
+  load_state_dict / optimizer steps invalidate them (sdpnet_train.AdamW, which
+  writes through raw addresses, bumps the counters itself); ``invalidate`` for
+  writes nobody can see.  Not part of the state_dict.
 """
 from __future__ import annotations
 
@@ -75,9 +77,30 @@ def _key(params, dtype, device):
     return (dtype, str(device)) + tuple((-1 if p.is_inference() else p._version, p.data_ptr()) for p in params)
 
 
+def _drop_cache(module: nn.Module, incompatible_keys=None) -> None:
+    """load_state_dict post-hook of every module that holds a cache: the copy into an inference
+    tensor (no version counter, _key) is a write the key cannot see."""
+    module.__dict__.pop("_sdp_cache", None)
+
+
+def invalidate(module: nn.Module) -> None:
+    """Drop the prepared-weight caches of ``module`` and its children; the next forward rebuilds
+    them from the parameters as they are.  For writes torch's version counters do not record:
+    ``p.data.mul_()`` / ``p.data.copy_()``, a kernel of your own writing through ``data_ptr()``.
+    (Optimizers, ``load_state_dict``, ``nn.init`` and in-place ops on ``p`` / ``p.detach()`` are
+    seen and need no call; sdpnet_train.AdamW marks what it writes.)"""
+    for m in module.modules():
+        m.__dict__.pop("_sdp_cache", None)
+
+
 def cached(module: nn.Module, name: str, params, dtype: torch.dtype, build: Callable[[], Dict]):
-    """Return module._sdp_cache[name] rebuilt when any param changed."""
-    cache = module.__dict__.setdefault("_sdp_cache", {})
+    """Return module._sdp_cache[name] rebuilt when any param changed (its version counter or its
+    address; see ``invalidate`` for the writes neither shows)."""
+    cache = module.__dict__.get("_sdp_cache")
+    if cache is None:
+        cache = module.__dict__["_sdp_cache"] = {}
+        if not any(h is _drop_cache for h in module._load_state_dict_post_hooks.values()):
+            module.register_load_state_dict_post_hook(_drop_cache)
     params = [p for p in params if p is not None]
     key = _key(params, dtype, params[0].device if params else "cpu")
     ent = cache.get(name)

@@ -1792,11 +1792,14 @@ class AdamW(torch.optim.Optimizer):
     ``update_scaler=False``.  Parameters whose ``grad`` is None are left out of the step
     (no decay, no moment update, no step count), as torch does.  The device work lists are
     rebuilt whenever a parameter, its state tensors or the set of parameters with gradients
-    change (``load_state_dict``, ``add_param_group``, a reallocated tensor)."""
+    change (``load_state_dict``, ``add_param_group``, a reallocated tensor).  Every ``step``
+    advances the version counter of each parameter it may have written (a skipped step included),
+    as an in-place torch update does."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, init_scale=65536.0,
                  growth_interval=2000):
         self._tables = None
+        self._written = []
         self._sig = None
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.growth_interval = growth_interval
@@ -1871,6 +1874,7 @@ class AdamW(torch.optim.Optimizer):
             self._tables.append(dict(params=ps, blocks=btab, nblocks=nblocks, sizes=sizes, pp=ptrs(ps),
                                      m1=ptrs([self.state[p]["exp_avg"] for p in ps]),
                                      m2=ptrs([self.state[p]["exp_avg_sq"] for p in ps]), steps=steps))
+        self._written = [p for ps in groups for p in ps]
         nb = sum(t["nblocks"] for t in self._tables)
         self._partials = torch.zeros(max(1, nb), dtype=torch.float32, device=dev)
         self._ensure_device_state(dev)
@@ -1939,4 +1943,9 @@ class AdamW(torch.optim.Optimizer):
         sp._check(L.sdp_adamw_finish(self.state_buf.data_ptr(), self.scaler.data_ptr() if update_scaler else None,
                                      2.0, 0.5, self.growth_interval, self._steps.data_ptr(), self._steps.numel(),
                                      stream), "adamw_finish")
+        # the kernel wrote the parameters through raw addresses: advance their version counters as an
+        # in-place torch op would, so everything keyed on them (the prepared-weight caches of
+        # sdpnet_engine.cached, autograd's saved-tensor check) sees the write.  Host only.  A skipped
+        # step is not known here without a sync; it bumps too, which costs a rebuild and nothing else.
+        torch.autograd.graph.increment_version(self._written)
         return loss
