@@ -43,7 +43,9 @@
  *                      output.  Scores, scale and softmax statistics are fp32.
  *       MFMA depthwise conv (tier 3): the LayerNorm'd input, the fp32 *weights* (to bf16,
  *                      once per launch), the output: bf16(bf16(LN(x)) (*) bf16(w) + bias).
- *                      Tiers 1 and 2 multiply by the fp32 weights.
+ *                      Tiers 1 and 2 multiply by the fp32 weights; tier 1 stages its band in LDS
+ *                      in the storage type, so it too rounds the LayerNorm'd input to bf16
+ *                      (tier 2 keeps it in fp32 registers).
  *       flash training attention: forward dropout(P) (un-normalised) for P V, and O; backward
  *                      dropout(P) (normalised by the saved LSE) for dV, dS = P o (dP - D) for dQ
  *                      and dK, with D = rowsum(dO o O) of the stored bf16 O; the outputs dQ,

@@ -369,10 +369,10 @@ SDP_DEV uint32_t pack_bf16x2(float a, float b) {
 }
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 
-// Partial LayerNorm statistics of one 8 x bf16 fragment: {sum x, sum x^2} with
-// v_dot2_f32_bf16 (fp32 accumulation), 8 instructions per fragment.
+// Head LayerNorm statistics of 8 x bf16 fragments, two passes over the registers (fp32).
 typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-SDP_DEV f32x2 frag_stats(const bf16x8& v, f32x2 acc) {
+// Sum of x over one fragment (the first pass), v_dot2_f32_bf16, 4 instructions per fragment.
+SDP_DEV float frag_sum(const bf16x8& v, float acc) {
   // (element-wise pairs: bit-casting a u32x4 lane to bf16x2 miscompiles in ROCm 7.2 hipcc,
   // every pair then reads dword 0)
   const bf16x8v v8 = __builtin_bit_cast(bf16x8v, v);
@@ -380,13 +380,27 @@ SDP_DEV f32x2 frag_stats(const bf16x8& v, f32x2 acc) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const bf16x2v x = {v8[2 * k], v8[2 * k + 1]};
-    acc.x = __builtin_amdgcn_fdot2_f32_bf16(x, one, acc.x, false);
-    acc.y = __builtin_amdgcn_fdot2_f32_bf16(x, x, acc.y, false);
+    acc = __builtin_amdgcn_fdot2_f32_bf16(x, one, acc, false);
+  }
+  return acc;
+}
+// Sum of (x - mean)^2 over one fragment (the second pass), packed f32: two partial sums.  The
+// one-pass E[x^2] - mean^2 cancels when a head's |mean| is far above its spread (gemm.hip's LN
+// partials: same reason).
+SDP_DEV f32x2 frag_sqdev(const bf16x8& v, float mean, f32x2 acc) {
+  const u32x4 w = __builtin_bit_cast(u32x4, v);
+  const f32x2 m2 = {mean, mean};
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const f32x2 d = f32x2{__uint_as_float(w[k] << 16), __uint_as_float(w[k] & 0xFFFF0000u)} - m2;
+    acc = d * d + acc;
   }
   return acc;
 }
 // y = (x - mean) * rstd * g + b on one fragment (g, b: its 8 columns), packed f32
-// math: y = x * t + (b - mean * t) with t = rstd * g.
+// math: y = (x - mean) * t + b with t = rstd * g (the difference first: x * t + (b - mean * t)
+// rounds b at the size of mean * t, whole bf16 ulps of y once a row's offset is far above its
+// spread; the operation count is the same).
 SDP_DEV bf16x8 frag_norm(const bf16x8& v, float mean, float rstd, const float* g, const float* b) {
   const u32x4 w = __builtin_bit_cast(u32x4, v);
   const f32x4 g0 = *(const f32x4*)g, g1 = *(const f32x4*)(g + 4);
@@ -399,8 +413,7 @@ SDP_DEV bf16x8 frag_norm(const bf16x8& v, float mean, float rstd, const float* g
     const f32x2 gg = k < 2 ? f32x2{g0[2 * k], g0[2 * k + 1]} : f32x2{g1[2 * k - 4], g1[2 * k - 3]};
     const f32x2 bb = k < 2 ? f32x2{b0[2 * k], b0[2 * k + 1]} : f32x2{b1[2 * k - 4], b1[2 * k - 3]};
     const f32x2 t = gg * r2;
-    const f32x2 c = t * m2 + bb;
-    const f32x2 y = x * t + c;
+    const f32x2 y = (x + m2) * t + bb;
     o[k] = pack_bf16x2(y.x, y.y);
   }
   return __builtin_bit_cast(bf16x8, o);
@@ -409,13 +422,17 @@ SDP_DEV bf16x8 frag_norm(const bf16x8& v, float mean, float rstd, const float* g
 template <int HDT>
 SDP_DEV void attn_norm_q(bf16x8 (&qf)[2 * HDT], bool qok, int hf, const float* gq, const float* bq, float eps) {
   constexpr int HD = 32 * HDT;
-  f32x2 st = {0.f, 0.f};
+  float sm = 0.f;
 #pragma unroll
-  for (int s = 0; s < 2 * HDT; ++s) st = frag_stats(qf[s], st);
-  st.x += __shfl_xor(st.x, 32, 64);
-  st.y += __shfl_xor(st.y, 32, 64);
-  const float qmean = st.x * (1.0f / HD);
-  const float qrstd = rsqrtf(fmaxf(st.y * (1.0f / HD) - qmean * qmean, 0.f) + eps);
+  for (int s = 0; s < 2 * HDT; ++s) sm = frag_sum(qf[s], sm);
+  sm += __shfl_xor(sm, 32, 64);
+  const float qmean = sm * (1.0f / HD);
+  f32x2 sq = {0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 2 * HDT; ++s) sq = frag_sqdev(qf[s], qmean, sq);
+  float m2 = sq.x + sq.y;
+  m2 += __shfl_xor(m2, 32, 64);
+  const float qrstd = rsqrtf(m2 * (1.0f / HD) + eps);
 #pragma unroll
   for (int s = 0; s < 2 * HDT; ++s) {
     const int d = 16 * s + 8 * hf;
@@ -1026,16 +1043,17 @@ SDP_DEV void attn_knorm32(bf16_t* Kd, int row0, int NP16, int lane, const float*
   bf16x8* kr = (bf16x8*)(Kd + (size_t)(ok ? row : 0) * HD);
   const int sw = (row >> 2) & 3;
   bf16x8 kv[NDS];
-  f32x2 st = {0.f, 0.f};
+  float sm = 0.f;
 #pragma unroll
   for (int i = 0; i < NDS; ++i) {
     kv[i] = kr[(NDS * hf + i) ^ sw];
-    st = frag_stats(kv[i], st);
+    sm = frag_sum(kv[i], sm);
   }
-  st.x = xhalf_sum(st.x);
-  st.y = xhalf_sum(st.y);
-  const float mean = st.x * (1.0f / HD);
-  const float rstd = rsqrtf(fmaxf(st.y * (1.0f / HD) - mean * mean, 0.f) + eps);
+  const float mean = xhalf_sum(sm) * (1.0f / HD);
+  f32x2 sq = {0.f, 0.f};
+#pragma unroll
+  for (int i = 0; i < NDS; ++i) sq = frag_sqdev(kv[i], mean, sq);
+  const float rstd = rsqrtf(xhalf_sum(sq.x + sq.y) * (1.0f / HD) + eps);
   if (ok) {
 #pragma unroll
     for (int i = 0; i < NDS; ++i) {
@@ -1507,7 +1525,7 @@ static int launch_attn_fa6(const void* QKV, int64_t ldq, void* O, int64_t ldo, i
 // workgroup = (b, h, <= 3 query tiles) + one producer wave.  The producer streams the head's
 // 32-row K / V tiles through a double-buffered LDS ring (padded rows, LD = HD + 8): lane l loads
 // row l & 31 of K (l < 32) or V, all CPR 16-B chunks in flight at once, k-normalises its K row in
-// registers (one-pass fp32 statistics, as attn_knorm32) and stores it; one barrier per key tile.
+// registers (two-pass fp32 statistics, as attn_knorm32) and stores it; one barrier per key tile.
 // Compute wave w owns query tile grp * qtw + w: q-norm on its fragments, then the online softmax
 // over the key tiles as they arrive (S^T = K Q^T and O^T += V^T P^T in the swapped 32x32x16 form,
 // exp2 argument folded into one FMA).  LDS 26 KiB per workgroup at hd = 96, so several workgroups
@@ -1546,11 +1564,14 @@ __global__ __launch_bounds__(256, 2) void attn_fs_bf16(const bf16_t* __restrict_
     };
     auto p_store = [&](int buf) {
       if (norm && mtx == 0) {
-        f32x2 st = {0.f, 0.f};
+        float sm = 0.f;
 #pragma unroll
-        for (int u = 0; u < CPR; ++u) st = frag_stats(pv[u], st);
-        const float mean = st.x * (1.0f / HD);
-        const float rstd = rsqrtf(fmaxf(st.y * (1.0f / HD) - mean * mean, 0.f) + eps);
+        for (int u = 0; u < CPR; ++u) sm = frag_sum(pv[u], sm);
+        const float mean = sm * (1.0f / HD);
+        f32x2 sq = {0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < CPR; ++u) sq = frag_sqdev(pv[u], mean, sq);
+        const float rstd = rsqrtf((sq.x + sq.y) * (1.0f / HD) + eps);
 #pragma unroll
         for (int u = 0; u < CPR; ++u) pv[u] = frag_norm(pv[u], mean, rstd, prm + 8 * u, prm + HD + 8 * u);
       }

@@ -90,13 +90,14 @@ SDP_DEV float gelu_erf_grad(float x) {  // Phi(x) + x phi(x)
 SDP_DEV float apply_act(int act, float x) {
   switch (act) {
     case ACT_GELU: return gelu_erf(x);  // erf GELU (nn.GELU())
-    case ACT_RELU: return fmaxf(x, 0.0f);
+    case ACT_RELU: return x < 0.0f ? 0.0f : x;  // (not fmaxf: a NaN stays a NaN, as torch's relu)
     case ACT_TANH: return tanhf(x);
     case ACT_SIGMOID: return 1.0f / (1.0f + expf(-x));
     case ACT_LEAKY_RELU: return x >= 0.0f ? x : 0.01f * x;
     case ACT_SELU: {
       const float alpha = 1.6732632423543772848f, scale = 1.0507009873554804934f;
-      return scale * (x > 0.0f ? x : alpha * (expf(x) - 1.0f));
+      // expm1f: expf(x) - 1 loses every digit of a small negative x to the rounding of expf at 1
+      return scale * (x > 0.0f ? x : alpha * expm1f(x));
     }
     case ACT_KELU: {
       const float a = 3.5f;
@@ -182,6 +183,14 @@ SDP_DEV float wave_sum(float v) {
 SDP_DEV float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// (fp64: the loss kernels and the fp32 softmax backward form their gradients, differences that
+// cancel, in double and round once)
+SDP_DEV double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 

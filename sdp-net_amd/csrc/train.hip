@@ -1756,11 +1756,14 @@ __global__ __launch_bounds__(256) void softmax_bwd_k(const T* __restrict__ P, in
     if (p > 0.f) g = uniform01(seed, (uint64_t)r * N + c) >= p ? g * kp : 0.f;
     return g;
   };
-  float dot = 0.f;
-  for (int c = lane; c < N; c += 64) dot += dpm(c) * to_f<T>(P[r * ldp + c]);
+  // fp32 rows: the dot product and P (dP - dot), a difference that cancels, in fp64, rounded once
+  // (a bf16 result is rounded far above the fp32 arithmetic's error: fp32 there)
+  using A = typename std::conditional<sizeof(T) == 4, double, float>::type;
+  A dot = 0;
+  for (int c = lane; c < N; c += 64) dot += (A)dpm(c) * (A)to_f<T>(P[r * ldp + c]);
   dot = wave_sum(dot);
   for (int c = lane; c < Npad; c += 64) {
-    const float v = c < N ? to_f<T>(P[r * ldp + c]) * (dpm(c) - dot) : 0.f;
+    const float v = c < N ? (float)((A)to_f<T>(P[r * ldp + c]) * ((A)dpm(c) - dot)) : 0.f;
     DS[r * ldds + c] = from_f<T>(v);
   }
 }
@@ -1852,8 +1855,9 @@ __global__ __launch_bounds__(256) void softmax_bwd_r(const T* __restrict__ P, in
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   const float kp = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+  using A = typename std::conditional<sizeof(T) == 4, double, float>::type;  // (as softmax_bwd_k)
   float pv[2][4], g[2][4];
-  float dot = 0.f;
+  A dot = 0;
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int c = 4 * (lane + 64 * i);
@@ -1866,7 +1870,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_r(const T* __restrict__ P, in
       for (int q = 0; q < 4; ++q) {
         if (c + q >= N) { g[i][q] = 0.f; pv[i][q] = 0.f; }
         else if (p > 0.f) g[i][q] = uniform01(seed, (uint64_t)r * N + c + q) >= p ? g[i][q] * kp : 0.f;
-        dot = fmaf(g[i][q], pv[i][q], dot);
+        dot = (A)g[i][q] * (A)pv[i][q] + dot;
       }
     }
   }
@@ -1877,7 +1881,7 @@ __global__ __launch_bounds__(256) void softmax_bwd_r(const T* __restrict__ P, in
     if (c < Npad) {
       float o[4];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) o[q] = pv[i][q] * (g[i][q] - dot);
+      for (int q = 0; q < 4; ++q) o[q] = (float)((A)pv[i][q] * ((A)g[i][q] - dot));
       store4<T>(DS + r * ldds + c, o);
     }
   }
@@ -2140,29 +2144,35 @@ __global__ __launch_bounds__(256) void ce_k(const T* __restrict__ L, int64_t ldl
       return;
     }
   }
+  // fp64 from here: the gradient softmax * sum t' - t' is a difference that cancels (a smoothed
+  // target against a probability of its size), and l - max spans the logits' whole range; in fp32
+  // either costs more digits than the result has.  B * K elements per step: the cost is nothing.
   const T* lp = L + r * ldl;
-  float mx = -INFINITY, sl = 0.f;
+  float mx = -INFINITY;
+  double sl = 0.0;
   for (int c = lane; c < K; c += 64) {
     const float v = to_f<T>(lp[c]);
     mx = fmaxf(mx, v);
-    sl += v;
+    sl += (double)v;
   }
   mx = wave_max(mx);
   sl = wave_sum(sl);
-  float se = 0.f;
-  for (int c = lane; c < K; c += 64) se += expf(to_f<T>(lp[c]) - mx);
+  const double mxd = (double)mx;
+  double se = 0.0;
+  for (int c = lane; c < K; c += 64) se += exp((double)to_f<T>(lp[c]) - mxd);
   se = wave_sum(se);
-  const float lse = mx + logf(se);
+  const double lse = mxd + log(se);
+  const double on = 1.0 - (double)eps, off = (double)eps / (double)K;
   int64_t lab = 0;
-  float li, tsum = 1.0f;
+  double li, tsum = 1.0;
   if constexpr (SOFT) {
     // -sum t'_k (l_k - lse) = lse * sum t' - sum t' l
     const float* tp = tg + r * ldt;
-    float st = 0.f, stl = 0.f;
+    double st = 0.0, stl = 0.0;
     for (int c = lane; c < K; c += 64) {
-      const float t = fmaf(1.0f - eps, tp[c], eps / (float)K);
+      const double t = fma(on, (double)tp[c], off);
       st += t;
-      stl = fmaf(t, to_f<T>(lp[c]), stl);
+      stl = fma(t, (double)to_f<T>(lp[c]), stl);
     }
     st = wave_sum(st);
     stl = wave_sum(stl);
@@ -2171,19 +2181,21 @@ __global__ __launch_bounds__(256) void ce_k(const T* __restrict__ L, int64_t ldl
   } else {
     lab = y[r];
     const bool ok = lab >= 0 && lab < K;
-    const float ly = ok ? to_f<T>(lp[lab]) : NAN;
-    li = (1.0f - eps) * (lse - ly) + eps * (lse - sl / (float)K);
+    const double ly = ok ? (double)to_f<T>(lp[lab]) : (double)NAN;
+    // (eps == 0: no smoothing term at all, as torch -- 0 * (lse - sl / K) is NaN once a class the
+    // label does not name has a -inf logit)
+    li = on * (lse - ly) + (eps != 0.f ? (double)eps * (lse - sl / (double)K) : 0.0);
   }
-  if (lane == 0) atomicAdd(loss, li / nrows);
+  if (lane == 0) atomicAdd(loss, (float)(li / (double)nrows));
   if (!D) return;
-  const float sc = grad_scale / nrows, inv = 1.0f / se;
-  const float bad = (!SOFT && !(lab >= 0 && lab < K)) ? NAN : 0.0f;
+  const double sc = (double)grad_scale / (double)nrows, inv = 1.0 / se;
+  const double bad = (!SOFT && !(lab >= 0 && lab < K)) ? (double)NAN : 0.0;
   for (int c = lane; c < K; c += 64) {
-    const float pr = expf(to_f<T>(lp[c]) - mx) * inv;
-    float tgt;
-    if constexpr (SOFT) tgt = fmaf(1.0f - eps, tg[r * ldt + c], eps / (float)K);
-    else tgt = (c == lab ? (1.0f - eps) : 0.0f) + eps / (float)K;
-    D[r * ldd + c] = from_f<T>(sc * (pr * tsum - tgt) + bad);
+    const double pr = exp((double)to_f<T>(lp[c]) - mxd) * inv;
+    double tgt;
+    if constexpr (SOFT) tgt = fma(on, (double)tg[r * ldt + c], off);
+    else tgt = (c == lab ? on : 0.0) + off;
+    D[r * ldd + c] = from_f<T>((float)(sc * (pr * tsum - tgt) + bad));
   }
 }
 
@@ -2379,14 +2391,16 @@ __global__ __launch_bounds__(256) void distill_k(const T* __restrict__ L, int64_
     lab = y[r];
     if (!(lab >= 0 && lab < K)) bad = NAN;
   }
-  const float on = 1.0f - eps, off = eps / (float)K, invT = 1.0f / temp;
+  // fp64 for everything but the maxima (as ce_k: the gradients are differences that cancel)
+  const double on = 1.0 - (double)eps, off = (double)eps / (double)K, invT = 1.0 / (double)temp;
   // pass 1: row maxima, the teacher's first argmax, sum of z (hard-label CE smoothing term)
-  float mz = -INFINITY, sl = 0.f, mt = -INFINITY;
+  float mz = -INFINITY, mt = -INFINITY;
+  double sl = 0.0;
   int am = INT_MAX;
   for (int c = lane; c < K; c += 64) {
     const float z = to_f<T>(lp[c]), t = to_f<TT>(tp[c]);
     mz = fmaxf(mz, z);
-    sl += z;
+    sl += (double)z;
     if (t > mt) {  // ascending c: the lowest index of this lane's maximum
       mt = t;
       am = c;
@@ -2404,26 +2418,27 @@ __global__ __launch_bounds__(256) void distill_k(const T* __restrict__ L, int64_
     }
   }
   if (am >= K) am = 0;  // a row with no value above -inf: stay inside the row
+  const double mzd = (double)mz, mtd = (double)mt;
   // pass 2: the exp sums and the base loss
-  float se = 0.f, seT = 0.f, stT = 0.f, acc = 0.f, st = 0.f, stl = 0.f, sb = 0.f;
+  double se = 0.0, seT = 0.0, stT = 0.0, acc = 0.0, st = 0.0, stl = 0.0, sb = 0.0;
   for (int c = lane; c < K; c += 64) {
-    const float z = to_f<T>(lp[c]), dz = z - mz;
-    if (!bce || hard) se += expf(dz);
+    const double z = (double)to_f<T>(lp[c]), dz = z - mzd;
+    if (!bce || hard) se += exp(dz);
     if (!hard) {
-      const float dt = to_f<TT>(tp[c]) - mt, et = expf(dt * invT);
-      seT += expf(dz * invT);
+      const double dt = (double)to_f<TT>(tp[c]) - mtd, et = exp(dt * invT);
+      seT += exp(dz * invT);
       stT += et;
-      if (et > 0.f) acc = fmaf(et, dt - dz, acc);
+      if (et > 0.0) acc = fma(et, dt - dz, acc);
     }
-    float yv;
-    if constexpr (SOFT) yv = fmaf(on, yp[c], off);
-    else yv = (c == lab ? on : 0.0f) + off;
+    double yv;
+    if constexpr (SOFT) yv = fma(on, (double)yp[c], off);
+    else yv = (c == lab ? on : 0.0) + off;
     if (bce) {
-      const float m = fmaxf(-z, 0.f);
-      sb += (1.0f - yv) * z + m + logf(expf(-m) + expf(-z - m));
+      const double m = fmax(-z, 0.0);
+      sb += (1.0 - yv) * z + m + log(exp(-m) + exp(-z - m));
     } else if constexpr (SOFT) {
       st += yv;
-      stl = fmaf(yv, z, stl);
+      stl = fma(yv, z, stl);
     }
   }
   se = wave_sum(se);
@@ -2433,42 +2448,43 @@ __global__ __launch_bounds__(256) void distill_k(const T* __restrict__ L, int64_
   st = wave_sum(st);
   stl = wave_sum(stl);
   sb = wave_sum(sb);
-  const float nrows = (float)B, inv_n = 1.0f / ((float)B * (float)K);
-  const float lse = mz + logf(se);
-  float base, tsum = 1.0f;
+  const double nrows = (double)B, inv_n = 1.0 / ((double)B * (double)K), badd = (double)bad;
+  const double lse = mzd + log(se);
+  double base, tsum = 1.0;
   if (bce) {
-    base = sb * inv_n + bad;
+    base = sb * inv_n + badd;
   } else if constexpr (SOFT) {
     tsum = st;
     base = (lse * st - stl) / nrows;
   } else {
-    const float ly = (bad == 0.0f) ? to_f<T>(lp[lab]) : NAN;
-    base = ((1.0f - eps) * (lse - ly) + eps * (lse - sl / (float)K)) / nrows;
+    const double ly = (bad == 0.0f) ? (double)to_f<T>(lp[lab]) : (double)NAN;
+    base = (on * (lse - ly) + (eps != 0.f ? (double)eps * (lse - sl / (double)K) : 0.0)) / nrows;
   }
-  float dist;
-  if (hard) dist = (lse - to_f<T>(lp[am])) / nrows;
-  else dist = temp * temp * (acc * invT / stT + (logf(seT) - logf(stT))) / nrows;
+  double dist;
+  if (hard) dist = (lse - (double)to_f<T>(lp[am])) / nrows;
+  else dist = (double)temp * (double)temp * (acc * invT / stT + (log(seT) - log(stT))) / nrows;
+  const double wb = 1.0 - (double)alpha, wa = (double)alpha;
   if (lane == 0) {
-    atomicAdd(loss, (1.0f - alpha) * base + alpha * dist);
+    atomicAdd(loss, (float)(wb * base + wa * dist));
     if (parts) {
-      atomicAdd(parts, base);
-      atomicAdd(parts + 1, dist);
+      atomicAdd(parts, (float)base);
+      atomicAdd(parts + 1, (float)dist);
     }
   }
   if (!D) return;
-  const float sc = grad_scale / nrows, scb = grad_scale * inv_n, wb = 1.0f - alpha;
-  const float inv = 1.0f / se, invz = 1.0f / seT, invt = 1.0f / stT;
+  const double sc = (double)grad_scale / nrows, scb = (double)grad_scale * inv_n;
+  const double inv = 1.0 / se, invz = 1.0 / seT, invt = 1.0 / stT;
   for (int c = lane; c < K; c += 64) {
-    const float z = to_f<T>(lp[c]), dz = z - mz;
-    float yv;
-    if constexpr (SOFT) yv = fmaf(on, yp[c], off);
-    else yv = (c == lab ? on : 0.0f) + off;
-    float bg, dg;
-    if (bce) bg = scb * (1.0f / (1.0f + expf(-z)) - yv) + bad;
-    else bg = sc * (expf(dz) * inv * tsum - yv) + bad;
-    if (hard) dg = sc * (expf(dz) * inv - (c == am ? 1.0f : 0.0f));
-    else dg = sc * temp * (expf(dz * invT) * invz - expf((to_f<TT>(tp[c]) - mt) * invT) * invt);
-    D[r * ldd + c] = from_f<T>(wb * bg + alpha * dg);
+    const double z = (double)to_f<T>(lp[c]), dz = z - mzd;
+    double yv;
+    if constexpr (SOFT) yv = fma(on, (double)yp[c], off);
+    else yv = (c == lab ? on : 0.0) + off;
+    double bg, dg;
+    if (bce) bg = scb * (1.0 / (1.0 + exp(-z)) - yv) + badd;
+    else bg = sc * (exp(dz) * inv * tsum - yv) + badd;
+    if (hard) dg = sc * (exp(dz) * inv - (c == am ? 1.0 : 0.0));
+    else dg = sc * (double)temp * (exp(dz * invT) * invz - exp(((double)to_f<TT>(tp[c]) - mtd) * invT) * invt);
+    D[r * ldd + c] = from_f<T>((float)(wb * bg + wa * dg));
   }
 }
 
