@@ -107,6 +107,31 @@ int sdp_gemm_ln(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_gstr
                 const float* ln_stats, const float* ln_colsum, float* part, void* stream);
 /* Which kernel sdp_gemm picks for a shape: 1 = 256x256 MFMA, 0 = generic. */
 int sdp_gemm_variant(int dtype, int M, int N, int K);
+/*
+ * Small-M GEMM for low-latency inference (opt-in: sdp_gemm / sdp_gemm_ln never take it).
+ * bf16 (dtype 1) only; operands, epilogue and row maps as sdp_gemm_ln, activation codes 0-7.
+ * Grid ceil(M / bm) x N / 64 x splits: a workgroup computes a bm x 64 tile over one of
+ * `splits` slices of whole 64-wide K-tiles.  splits > 1: every slice writes its fp32 slab
+ * ws[s][m][n] and a second launch sums the slabs in slice order 0 .. splits-1 and runs the
+ * epilogue, so the result depends on (bm, splits) only through that fixed summation order,
+ * never on the order workgroups run in.  One bf16 rounding, bf16(act(acc + b [+ R]) [+ R])
+ * (fast GEMM 9's model); GELU as the fast GEMM (tanh form unless sdp_gemm_set_exact_gelu(1)).
+ * part: {mean, M2} of the stored row's 64-column chunks, layout as sdp_gemm_ln.
+ * The library keeps no state: ws is the caller's, at least sdp_gemm_splitk_ws_bytes() bytes,
+ * 16-byte aligned (may be NULL when splits == 1), and is only used until the call's launches
+ * finish on `stream`.  Returns hipErrorInvalidValue without launching when bm is not 64 / 128,
+ * splits is outside [1, K / 64], N % 64 or K % 64 is non-zero, ws_bytes is too small, or an
+ * operand misses its alignment (X, W: 16-byte rows; Y, R: 8-byte rows; bias, ln_colsum: 16 bytes).
+ */
+int sdp_gemm_splitk(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_gstride, int x_off,
+                    const void* W, int64_t ldw, const float* bias, const void* R, int64_t ldr,
+                    int r_grp, int64_t r_gstride, int r_off, void* Y, int64_t ldy, int y_grp,
+                    int64_t y_gstride, int y_off, int M, int N, int K, int act, int resid_pre,
+                    const float* ln_stats, const float* ln_colsum, float* part, int bm, int splits,
+                    void* ws, int64_t ws_bytes, void* stream);
+/* Workspace bytes of sdp_gemm_splitk: splits * M * N * 4 for splits > 1, else 0; -1 for
+ * invalid arguments. */
+int64_t sdp_gemm_splitk_ws_bytes(int M, int N, int bm, int splits);
 /* Test hook: force the generic kernel (returns the previous setting). */
 int sdp_gemm_force_generic(int on);
 /* Select the bf16 fast kernel: 14 = 8-phase ping-pong 256x256x64 with the

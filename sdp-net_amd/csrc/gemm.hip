@@ -23,6 +23,8 @@
 //    Requires K % 64 == 0; any M, N (clamped loads, masked stores).
 //  * gemm_generic<T> — correctness path for fp32 (exact f32 MFMA
 //    v_mfma_f32_16x16x4_f32) and for odd bf16 shapes; fully masked.
+//  * small::gemm_bf16_splitk + small::splitk_reduce — opt-in small-M path (sdp_gemm_splitk
+//    only; sdp_gemm never routes to it): BM x 64 tiles over K-slices, fp32 slabs.
 //
 // The MFMA is issued "swapped" (A-operand = W rows, B-operand = X rows) so the
 // accumulator holds D[n][m] with 4 consecutive n per lane: every epilogue
@@ -1488,6 +1490,202 @@ __global__ __launch_bounds__(256) void gemm_generic(const T* __restrict__ X, int
 }  // namespace gen
 
 // ---------------------------------------------------------------------------
+// Small-M kernel (opt-in, sdp_gemm_splitk): bf16, BM x 64 x 64 tiles over one K-slice.
+// The 256x256 kernel gives a 196-row GEMM 3..12 workgroups, each walking the whole K; here the
+// grid is ceil(M/BM) x N/64 x S, every workgroup a BM x 64 output tile over one of S slices of
+// whole 64-wide K-tiles (slice sizes differ by at most one tile).  4 waves (2 along M x 2 along
+// N), v_mfma_f32_16x16x32_bf16 issued swapped as above; both operands go HBM -> registers ->
+// ds_write_b128 into the XOR-swizzled [row][64] image of the hot kernel (full 128-B rows per 8
+// lanes), double buffered, one barrier per K-tile, the next tile's global loads in flight under
+// the current tile's MFMAs.
+// S == 1: the fp32 tile goes through LDS to the row epilogue below.  S > 1: every slice stores
+// its fp32 slab ws[s][m][n] and splitk_reduce (a second launch: nothing inside a launch waits on
+// another workgroup) sums the slabs in slice order and runs the same epilogue, so the result
+// does not depend on the order workgroups run in.
+// ---------------------------------------------------------------------------
+namespace small {
+constexpr int BN = 64, BK = 64, NTHREADS = 256;
+constexpr int TLD = BN + 4;  // fp32 tile row stride in LDS (floats; rows stay 16-B aligned)
+
+// Epilogue of 4 consecutive columns n..n+3 of logical row m; the 16 lanes l..l+15 (l % 16 == 0) of
+// a wave hold the row's 64-column chunk.  One rounding: bf16(act(acc + b [+ R]) [+ R]) (kernel 9's
+// arithmetic).  part: {mean, M2} of the 64 stored bf16 values in two passes (sum, then squared
+// deviations from its mean), the whole-line epilogue's layout.  Rows past M come in clamped with
+// row_ok = false: they take part in the shuffles and store nothing.
+SDP_DEV void row_epilogue(const Epi<bf16_t>& e, int m, bool row_ok, int n, int N, f32x4 acc, int fast_gelu) {
+  float v[4] = {acc[0], acc[1], acc[2], acc[3]};
+  const f32x4 bv = e.bias ? *(const f32x4*)(e.bias + n) : f32x4{0.f, 0.f, 0.f, 0.f};
+  if (e.lnst) {
+    const float2 st = *(const float2*)(e.lnst + 2 * (int64_t)m);
+    const float rmu = st.y * st.x;
+    const f32x4 sv = *(const f32x4*)(e.lnsum + n);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = ln_fold(v[r], st.y, rmu, sv[r], bv[r]);
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] += bv[r];
+  }
+  float rv[4] = {0.f, 0.f, 0.f, 0.f};
+  if (e.resid) {
+    const bf16x4 rr = *(const bf16x4*)(e.resid + e.rmap(m) * e.ldr + n);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) rv[r] = bf2f((bf16_t)rr[r]);
+  }
+  if (e.resid && e.resid_pre) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] += rv[r];
+  }
+  if (e.act != ACT_NONE) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = fast_gelu ? gelu_fast(v[r]) : apply_act(e.act, v[r]);
+  }
+  if (e.resid && !e.resid_pre) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] += rv[r];
+  }
+  bf16x4 o;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) o[r] = (short)f2bf(v[r]);
+  const int64_t prow = e.cmap(m);
+  if (row_ok) *(bf16x4*)(e.out + prow * e.ldc + n) = o;
+  if (e.part) {
+    float f[4], sum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      f[r] = bf2f((bf16_t)o[r]);
+      sum += f[r];
+    }
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) sum += __shfl_xor(sum, d, 64);
+    const float mean = sum * (1.0f / 64.0f);
+    float m2 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) m2 = fmaf(f[r] - mean, f[r] - mean, m2);
+#pragma unroll
+    for (int d = 1; d < 16; d <<= 1) m2 += __shfl_xor(m2, d, 64);
+    if (row_ok && (threadIdx.x & 15) == 0)
+      *(float2*)(e.part + (prow * (N >> 6) + (n >> 6)) * 2) = float2{mean, m2};
+  }
+}
+
+template <int BM>
+__global__ __launch_bounds__(NTHREADS) void gemm_bf16_splitk(const bf16_t* __restrict__ X, int64_t ldx, RowMap xmap,
+                                                             const bf16_t* __restrict__ W, int64_t ldw,
+                                                             Epi<bf16_t> epi, float* __restrict__ ws, int M, int N,
+                                                             int K, int S, int fast_gelu) {
+  constexpr int MT = BM / 32;  // 16-row m-tiles per wave = 32-row load passes per workgroup
+  constexpr int XT = BM * 128, STAGE = XT + BN * 128;
+  static_assert(BM * TLD * 4 <= 2 * STAGE, "the fp32 tile reuses the operand stages");
+  __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
+  const int m0 = blockIdx.x * BM, n0 = blockIdx.y * BN, sl = blockIdx.z;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, fr = lane & 15, fq = lane >> 4;
+  // this slice's K-tiles: [t0, t0 + nt)
+  const int kt = K / BK, tb = kt / S, trem = kt % S;
+  const int t0 = sl * tb + min(sl, trem), nt = tb + (sl < trem ? 1 : 0);
+
+  // loads: thread -> 16-B chunk lc of rows lr + 32 i (8 lanes cover a row's 128 B); rows past M
+  // re-read row M - 1 (their results are never stored)
+  const int lc = tid & 7, lr = tid >> 3;
+  const bf16_t* xp[MT];
+  const bf16_t* wp[2];
+#pragma unroll
+  for (int i = 0; i < MT; ++i) xp[i] = X + xmap(min(m0 + lr + 32 * i, M - 1)) * ldx + (int64_t)t0 * BK + lc * 8;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) wp[i] = W + (int64_t)(n0 + lr + 32 * i) * ldw + (int64_t)t0 * BK + lc * 8;
+  bf16x8 xr[MT], wr[2];
+  auto gload = [&](int t) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i) xr[i] = *(const bf16x8*)(xp[i] + t * BK);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) wr[i] = *(const bf16x8*)(wp[i] + t * BK);
+  };
+  auto lstore = [&](char* st) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      const int r = lr + 32 * i;
+      *(bf16x8*)(st + r * 128 + fast::swz(r, lc) * 16) = xr[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int r = lr + 32 * i;
+      *(bf16x8*)(st + XT + r * 128 + fast::swz(r, lc) * 16) = wr[i];
+    }
+  };
+
+  f32x4 acc[2][MT];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < MT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  gload(0);
+  lstore(lds);
+  __syncthreads();
+  for (int t = 0; t < nt; ++t) {
+    const char* st = lds + (t & 1) * STAGE;
+    if (t + 1 < nt) gload(t + 1);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      bf16x8 aw[2], bx[MT];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) aw[i] = fast::lds_frag(st + XT, wn * 32 + i * 16 + fr, kk * 4 + fq);
+#pragma unroll
+      for (int j = 0; j < MT; ++j) bx[j] = fast::lds_frag(st, wm * (BM / 2) + j * 16 + fr, kk * 4 + fq);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < MT; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(aw[i], bx[j], acc[i][j], 0, 0, 0);
+    }
+    // the other stage was last read in iteration t - 1, which every wave left through the barrier
+    if (t + 1 < nt) lstore(lds + ((t + 1) & 1) * STAGE);
+    __syncthreads();
+  }
+
+  // D[n][m]: the lane holds n = .. + 4 fq + r, m = .. + fr
+  if (S > 1) {
+    float* slab = ws + (int64_t)sl * M * N;
+#pragma unroll
+    for (int j = 0; j < MT; ++j) {
+      const int m = m0 + wm * (BM / 2) + j * 16 + fr;
+      if (m >= M) continue;
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        *(f32x4*)(slab + (int64_t)m * N + n0 + wn * 32 + i * 16 + fq * 4) = acc[i][j];
+    }
+    return;
+  }
+  float* tile = (float*)lds;  // every wave is past the K-loop's last barrier
+#pragma unroll
+  for (int j = 0; j < MT; ++j)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      *(f32x4*)(tile + (wm * (BM / 2) + j * 16 + fr) * TLD + wn * 32 + i * 16 + fq * 4) = acc[i][j];
+  __syncthreads();
+  const int g = tid >> 4, l = tid & 15;
+  for (int p = 0; p < BM / 16; ++p) {
+    const int row = p * 16 + g, m = m0 + row;
+    row_epilogue(epi, min(m, M - 1), m < M, n0 + l * 4, N, *(const f32x4*)(tile + row * TLD + l * 4), fast_gelu);
+  }
+}
+
+// Sum of the S slabs in slice order 0 .. S-1 (fp32), then the row epilogue: 16 rows x one
+// 64-column chunk per workgroup, 16 lanes x 4 columns per row.
+__global__ __launch_bounds__(NTHREADS) void splitk_reduce(const float* __restrict__ ws, Epi<bf16_t> epi, int M, int N,
+                                                          int S, int fast_gelu) {
+  const int g = threadIdx.x >> 4, l = threadIdx.x & 15;
+  const int m = blockIdx.x * 16 + g, n = blockIdx.y * BN + l * 4;
+  const int mc = min(m, M - 1);
+  const float* p = ws + (int64_t)mc * N + n;
+  const int64_t slab = (int64_t)M * N;
+  f32x4 a = *(const f32x4*)p;
+  for (int s = 1; s < S; ++s) a += *(const f32x4*)(p + s * slab);
+  row_epilogue(epi, mc, m < M, n, N, a, fast_gelu);
+}
+}  // namespace small
+
+// ---------------------------------------------------------------------------
 // C ABI
 // ---------------------------------------------------------------------------
 static RowMap mk_map(int grp, int64_t gstride, int off) {
@@ -1869,6 +2067,59 @@ static int gemm_impl(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x
                        (const float*)W, ldw, e, M, N, K);
   } else {
     return (int)hipErrorInvalidValue;
+  }
+  return SDP_CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------------------
+// Split-K small-M GEMM (opt-in; sdp_gemm / sdp_gemm_ln never route here).  bf16 only.  The
+// library keeps no state for it: the caller chooses bm / splits and owns the workspace.
+// ---------------------------------------------------------------------------
+extern "C" int64_t sdp_gemm_splitk_ws_bytes(int M, int N, int bm, int splits) {
+  if (M < 0 || N <= 0 || (bm != 64 && bm != 128) || splits < 1) return -1;
+  return splits > 1 ? (int64_t)splits * M * N * 4 : 0;
+}
+
+extern "C" int sdp_gemm_splitk(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_gstride, int x_off,
+                               const void* W, int64_t ldw, const float* bias, const void* R, int64_t ldr,
+                               int r_grp, int64_t r_gstride, int r_off, void* Y, int64_t ldy, int y_grp,
+                               int64_t y_gstride, int y_off, int M, int N, int K, int act, int resid_pre,
+                               const float* ln_stats, const float* ln_colsum, float* part, int bm, int splits,
+                               void* ws, int64_t ws_bytes, void* stream) {
+  if (dtype != 1 || M < 0 || N <= 0 || K <= 0 || !X || !W || !Y || act < 0 || act > ACT_KELU)
+    return (int)hipErrorInvalidValue;
+  if ((ln_stats != nullptr) != (ln_colsum != nullptr)) return (int)hipErrorInvalidValue;
+  if ((bm != 64 && bm != 128) || N % small::BN || K % small::BK || splits < 1 || splits > K / small::BK)
+    return (int)hipErrorInvalidValue;
+  if (N / small::BN > 65535 || splits > 65535) return (int)hipErrorInvalidValue;
+  const int64_t need = sdp_gemm_splitk_ws_bytes(M, N, bm, splits);
+  if (need > 0 && (!ws || ws_bytes < need || (uintptr_t)ws % 16)) return (int)hipErrorInvalidValue;
+  // 16-B operand chunks, 8-B output / residual vectors, 16-B bias / column-sum vectors
+  auto al = [](const void* p, uintptr_t a) { return (uintptr_t)p % a == 0; };
+  if (ldx % 8 || ldw % 8 || !al(X, 16) || !al(W, 16) || ldy % 4 || !al(Y, 8) || (R && (ldr % 4 || !al(R, 8))) ||
+      (bias && !al(bias, 16)) || (ln_colsum && !al(ln_colsum, 16)) || (ln_stats && !al(ln_stats, 8)) ||
+      (part && !al(part, 8)))
+    return (int)hipErrorInvalidValue;
+  if (M == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const RowMap xm = mk_map(x_grp, x_gstride, x_off);
+  Epi<bf16_t> e{bias, (const bf16_t*)R, ldr, mk_map(r_grp, r_gstride, r_off), (bf16_t*)Y, ldy,
+                mk_map(y_grp, y_gstride, y_off), act, resid_pre, ln_stats, ln_colsum, part};
+  // GELU in the fast kernel's form (tanh unless sdp_gemm_set_exact_gelu(1)): the activation
+  // function must not change with the batch size
+  const int fast_gelu = (act == ACT_GELU && !g_exact_gelu) ? 1 : 0;
+  const dim3 grid((M + bm - 1) / bm, N / small::BN, splits);
+  if (bm == 64)
+    hipLaunchKernelGGL(small::gemm_bf16_splitk<64>, grid, dim3(small::NTHREADS), 0, s, (const bf16_t*)X, ldx, xm,
+                       (const bf16_t*)W, ldw, e, (float*)ws, M, N, K, splits, fast_gelu);
+  else
+    hipLaunchKernelGGL(small::gemm_bf16_splitk<128>, grid, dim3(small::NTHREADS), 0, s, (const bf16_t*)X, ldx, xm,
+                       (const bf16_t*)W, ldw, e, (float*)ws, M, N, K, splits, fast_gelu);
+  if (splits > 1) {
+    const int rc = SDP_CHECK_LAUNCH();
+    if (rc) return rc;
+    hipLaunchKernelGGL(small::splitk_reduce, dim3((M + 15) / 16, N / small::BN), dim3(small::NTHREADS), 0, s,
+                       (const float*)ws, e, M, N, splits, fast_gelu);
   }
   return SDP_CHECK_LAUNCH();
 }

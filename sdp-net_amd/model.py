@@ -186,7 +186,8 @@ class MainModel(SdPModel):
                 return torch.ops.sdpnet.main_forward_raw(x, self._sdp_handle, num_registers, code)
             return torch.ops.sdpnet.main_forward(x, self._sdp_handle, num_registers, code)
         if _hooked(self):
-            return self._forward_modules(x, num_registers, return_raw_outputs)
+            with sp.low_latency(self._low_latency_on()):
+                return self._forward_modules(x, num_registers, return_raw_outputs)
         if self._fp32_stream_eval(x):
             import sdpnet_train
             return sdpnet_train.eval_forward(self, x, num_registers, return_raw_outputs)
@@ -204,8 +205,20 @@ class MainModel(SdPModel):
             on = _EVAL_FP32_STREAM
         return bool(on) and x.is_cuda and compute_dtype(x, self) == torch.bfloat16
 
+    def _low_latency_on(self) -> bool:
+        """Small-batch eval GEMMs on the split-K kernel (sdpnet_hip.low_latency): model.low_latency
+        = True / False, or None (the default) for SDPNET_LOW_LATENCY (unset: whatever an enclosing
+        ``with sdpnet_hip.low_latency():`` says, i.e. off by default).  Read where the kernels are
+        launched, so the torch.compile custom op honours it as well.  Train mode never looks at it."""
+        on = getattr(self, "low_latency", None)
+        if on is None:
+            env = os.environ.get("SDPNET_LOW_LATENCY")
+            on = sp.low_latency_enabled() if env is None else env != "0"
+        return bool(on)
+
     def _fused_forward(self, x: torch.Tensor, num_registers: int, dt, return_raw_outputs: bool):
-        with torch.no_grad():
+        # (also the body of the torch.compile custom ops, sdpnet_ops.main_forward[_raw])
+        with torch.no_grad(), sp.low_latency(self._low_latency_on()):
             B, _, Hi, Wi = x.shape
             p = self.conv_init.patch_size
             Hp, Wp = Hi // p, Wi // p

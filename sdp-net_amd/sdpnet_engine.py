@@ -77,9 +77,14 @@ def _key(params, dtype, device):
     return (dtype, str(device)) + tuple((-1 if p.is_inference() else p._version, p.data_ptr()) for p in params)
 
 
+_INVALIDATIONS = 0  # bumped by every invalidation the version key cannot show (GraphedForward watches it)
+
+
 def _drop_cache(module: nn.Module, incompatible_keys=None) -> None:
     """load_state_dict post-hook of every module that holds a cache: the copy into an inference
     tensor (no version counter, _key) is a write the key cannot see."""
+    global _INVALIDATIONS
+    _INVALIDATIONS += 1
     module.__dict__.pop("_sdp_cache", None)
 
 
@@ -89,6 +94,8 @@ def invalidate(module: nn.Module) -> None:
     ``p.data.mul_()`` / ``p.data.copy_()``, a kernel of your own writing through ``data_ptr()``.
     (Optimizers, ``load_state_dict``, ``nn.init`` and in-place ops on ``p`` / ``p.detach()`` are
     seen and need no call; sdpnet_train.AdamW marks what it writes.)"""
+    global _INVALIDATIONS
+    _INVALIDATIONS += 1
     for m in module.modules():
         m.__dict__.pop("_sdp_cache", None)
 
@@ -139,3 +146,70 @@ def hooked(module: nn.Module) -> bool:
         if m._forward_hooks or m._forward_pre_hooks:
             return True
     return False
+
+
+class GraphedForward:
+    """One eval forward of ``model`` captured into a HIP graph and replayed per call: the forward's
+    several hundred launches become one, which is most of the latency at small batch.
+
+    ``GraphedForward(model, example, num_registers=3)`` warms up (which builds the prepared-weight
+    caches) and captures ``model(example, num_registers)`` into a static input and static logits.
+    ``gf(x)`` copies ``x`` into the static input, replays and returns the static logits: the SAME
+    tensor every call, overwritten by the next call (clone it to keep it).  ``x`` must have the
+    example's shape, dtype and device.
+
+    A replay never computes with stale prepared weights: every call compares the version key
+    ``cached`` uses (version counter and address of every parameter) and the count of
+    ``invalidate`` / ``load_state_dict`` calls with those of the capture, and captures again when
+    either changed, or when the model's low_latency setting did.  Whatever ``model(x)`` would run
+    eagerly is what is captured (streams, low_latency, final_rows ...); no environment variable
+    and no queue setting is touched."""
+
+    def __init__(self, model: nn.Module, example: torch.Tensor, num_registers: int = 3):
+        if model.training:
+            raise RuntimeError("GraphedForward captures the eval forward: call model.eval() first")
+        if not example.is_cuda:
+            raise RuntimeError("GraphedForward needs a CUDA (ROCm) example input")
+        self.model = model
+        self.num_registers = num_registers
+        self._x = example.detach().clone(memory_format=torch.contiguous_format)
+        self._graph = None
+        self._y = None
+        self._state = None
+        self.captures = 0
+        self._capture()
+
+    def _current_state(self):
+        ll = getattr(self.model, "_low_latency_on", None)
+        return (_key(list(self.model.parameters()), self._x.dtype, self._x.device), _INVALIDATIONS,
+                ll() if ll is not None else sp.low_latency_enabled())
+
+    def _capture(self):
+        dev = self._x.device
+        self._graph = self._y = None  # the old graph's pool goes before the new one is built
+        with torch.no_grad(), torch.cuda.device(dev):
+            cur = torch.cuda.current_stream(dev)
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(cur)
+            with torch.cuda.stream(side):  # warm-up off the capture: weight caches, stream pool, allocator
+                for _ in range(2):
+                    self.model(self._x, self.num_registers)
+            cur.wait_stream(side)
+            state = self._current_state()  # after the warm-up: building a cache must not look like a change
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                y = self.model(self._x, self.num_registers)
+        self._graph, self._y, self._state = graph, y, state
+        self.captures += 1
+
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        if x.shape != self._x.shape or x.dtype != self._x.dtype or x.device != self._x.device:
+            raise ValueError(f"GraphedForward was captured for {tuple(self._x.shape)} {self._x.dtype} on "
+                             f"{self._x.device}, got {tuple(x.shape)} {x.dtype} on {x.device}")
+        if self.model.training:
+            raise RuntimeError("GraphedForward replays the eval forward; the model is in train mode")
+        self._x.copy_(x)
+        if self._current_state() != self._state:
+            self._capture()
+        self._graph.replay()
+        return self._y

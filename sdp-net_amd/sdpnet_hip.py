@@ -37,6 +37,9 @@ _SIGS = {
     "sdp_gemm_ln": ([_i32, _vp, _i64, *_ROWMAP, _vp, _i64, _vp, _vp, _i64, *_ROWMAP, _vp, _i64, *_ROWMAP,
                      _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp], _i32),
     "sdp_gemm_variant": ([_i32, _i32, _i32, _i32], _i32),
+    "sdp_gemm_splitk": ([_i32, _vp, _i64, *_ROWMAP, _vp, _i64, _vp, _vp, _i64, *_ROWMAP, _vp, _i64, *_ROWMAP,
+                         _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp], _i32),
+    "sdp_gemm_splitk_ws_bytes": ([_i32, _i32, _i32, _i32], _i64),
     "sdp_gemm_force_generic": ([_i32], _i32),
     "sdp_gemm_set_fast_kernel": ([_i32], _i32),
     "sdp_gemm_set_store_policy": ([_i32], _i32),
@@ -290,7 +293,9 @@ def gemm(x: Rows, w: torch.Tensor, y: Rows, M: int, N: int, K: int, bias: Option
     """y = epilogue(x . w^T).  ln = (stats [M,2] (mean, rstd) per logical row of x,
     colsum [N] of the LN-folded weight): LayerNorm folded into the GEMM
     (w = W * gamma, bias = beta . W^T + b).  part: token-row partial statistics
-    buffer [rows, ceil(N/64), 2] the output rows' {mean, M2} are written to."""
+    buffer [rows, ceil(N/64), 2] the output rows' {mean, M2} are written to.
+    While ``low_latency`` is on, a bf16 call that ``gemm_split_plan`` takes (and whose operands
+    have the alignment) runs on ``gemm_splitk`` instead; fp32 calls never do."""
     _need_cuda(x.t, w, y.t, bias)
     dt = dcode(x.t.dtype)
     _req(w.dtype == x.t.dtype == y.t.dtype and w.is_contiguous() and w.shape[0] >= N)
@@ -300,6 +305,11 @@ def gemm(x: Rows, w: torch.Tensor, y: Rows, M: int, N: int, K: int, bias: Option
         r = [resid.t.data_ptr(), resid.ld, *resid.map()]
     else:
         r = [None, 0, 0, 0, 0]
+    if _LOW_LATENCY and dt == BF16:
+        plan = gemm_split_plan(M, N, K, _cus(y.t.device))
+        if plan is not None and _splitk_aligned(x, w, y, bias, resid, ln, part):
+            return gemm_splitk(x, w, y, M, N, K, plan[0], plan[1], bias=bias, resid=resid, act=act,
+                               resid_pre=resid_pre, ln=ln, part=part)
     tl = _TL
     if tl is not None:
         slot0 = lib().sdp_gemm_timeline_count()
@@ -318,6 +328,147 @@ def gemm(x: Rows, w: torch.Tensor, y: Rows, M: int, N: int, K: int, bias: Option
         es = x.t.element_size()
         nbytes = es * (M * K + N * K + M * N * (2 if resid is not None else 1)) + (4 * N if bias is not None else 0)
         tl.append((slot0, M, N, K, 2.0 * M * N * K, nbytes))
+
+
+# ---------------------------------------------------------------------------
+# Low-latency inference: small-M bf16 GEMMs on the split-K kernel (opt-in).
+_LOW_LATENCY = False
+_CUS = {}
+
+
+def set_low_latency(on: bool) -> bool:
+    """Route planned bf16 ``gemm()`` calls (``gemm_split_plan``) to ``gemm_splitk``; returns the
+    previous value.  Off by default.  fp32 calls and the training entry points are never routed."""
+    global _LOW_LATENCY
+    old, _LOW_LATENCY = _LOW_LATENCY, bool(on)
+    return old
+
+
+def low_latency_enabled() -> bool:
+    return _LOW_LATENCY
+
+
+class low_latency:
+    """``with low_latency(on=True):`` -- set_low_latency for the block, restored on exit."""
+
+    def __init__(self, on: bool = True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = set_low_latency(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_low_latency(self.old)
+        return False
+
+
+def _cus(dev: torch.device) -> int:
+    i = dev.index if dev.index is not None else torch.cuda.current_device()
+    if i not in _CUS:
+        _CUS[i] = int(torch.cuda.get_device_properties(i).multi_processor_count)
+    return _CUS[i]
+
+
+def gemm_split_plan(M: int, N: int, K: int, cus: int = 256) -> Optional[Tuple[int, int]]:
+    """(bm, splits) of ``gemm_splitk`` for a bf16 GEMM, or None: today's kernels.
+
+    A pure function of its arguments (no library call).  None when N or K is no multiple of 64, or
+    when the 256x256 kernel's own grid ceil(M/256) * ceil(N/256) exceeds half of ``cus`` (it fills
+    the chip: the throughput path stays as it is).  Otherwise
+
+    * splits = cus // (4 * N/64), within [1, K/64]: sized so that ONE image's token rows (about 200:
+      four 64-row tiles) give a grid of about one workgroup per CU.  It does not depend on M, and
+      the K-slices alone decide the summation order, so with the switch on a row's result does not
+      depend on the batch it runs in for as long as the shape stays planned (bm does not enter the
+      arithmetic);
+    * bm = 64 while that keeps the grid within ``cus`` workgroups, else 128;
+    * None when even 128-row tiles give more than two workgroups per CU
+    (DESIGN.md, "Low-latency path")."""
+    if M < 1 or N < 64 or K < 64 or N % 64 or K % 64 or cus < 1:
+        return None
+    if -(-M // 256) * -(-N // 256) > cus // 2:
+        return None
+    nt, kt = N // 64, K // 64
+    splits = max(1, min(kt, cus // (4 * nt)))
+    bm = 64 if -(-M // 64) * nt * splits <= cus else 128
+    if -(-M // bm) * nt * splits > 2 * cus:
+        return None
+    return bm, splits
+
+
+def _max_row(r: Rows, M: int) -> int:
+    """Largest physical row the logical rows 0 .. M-1 of ``r`` reach."""
+    if r.grp <= 0:
+        return M - 1
+    g = (M - 1) // r.grp
+    last = g * r.gstride + r.off + (M - 1) % r.grp
+    return max(last, (g - 1) * r.gstride + r.off + r.grp - 1) if g > 0 else last
+
+
+def _fits(t: torch.Tensor, elems: int) -> bool:
+    return t.storage_offset() * t.element_size() + elems * t.element_size() <= t.untyped_storage().nbytes()
+
+
+def _splitk_aligned(x: Rows, w: torch.Tensor, y: Rows, bias, resid: Optional[Rows], ln, part) -> bool:
+    """The operand alignment sdp_gemm_splitk asks for (a call that misses it keeps today's path)."""
+    ok = (x.ld % 8 == 0 and w.stride(0) % 8 == 0 and x.t.data_ptr() % 16 == 0 and w.data_ptr() % 16 == 0
+          and y.ld % 4 == 0 and y.t.data_ptr() % 8 == 0)
+    if resid is not None:
+        ok = ok and resid.ld % 4 == 0 and resid.t.data_ptr() % 8 == 0
+    if bias is not None:
+        ok = ok and bias.data_ptr() % 16 == 0
+    if ln is not None:
+        ok = ok and ln[0].data_ptr() % 8 == 0 and ln[1].data_ptr() % 16 == 0
+    if part is not None:
+        ok = ok and part.data_ptr() % 8 == 0
+    return ok
+
+
+def gemm_splitk_ws_bytes(M: int, N: int, bm: int, splits: int) -> int:
+    return int(lib().sdp_gemm_splitk_ws_bytes(M, N, bm, splits))
+
+
+def gemm_splitk(x: Rows, w: torch.Tensor, y: Rows, M: int, N: int, K: int, bm: int, splits: int,
+                bias: Optional[torch.Tensor] = None, resid: Optional[Rows] = None, act: int = 0,
+                resid_pre: bool = False, ln: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                part: Optional[torch.Tensor] = None, ws: Optional[torch.Tensor] = None):
+    """y = epilogue(x . w^T) on the small-M split-K kernel (bf16; arguments as ``gemm``).
+    bm in {64, 128}: rows per workgroup tile; splits in [1, K/64]: K-slices, summed in slice
+    order by a second launch.  ws: fp32 workspace of at least gemm_splitk_ws_bytes(); None takes
+    it from torch's allocator on the current stream (stream-ordered: safe under graph capture
+    and on the model's sub-batch streams)."""
+    _need_cuda(x.t, w, y.t, bias, ws)
+    _req(x.t.dtype == torch.bfloat16, "gemm_splitk is bf16 only")
+    _req(w.dtype == x.t.dtype == y.t.dtype and w.is_contiguous() and w.shape[0] >= N)
+    _req(M >= 0 and N > 0 and K > 0 and w.shape[-1] >= K and w.stride(0) >= K, "shape")
+    _req(bm in (64, 128) and N % 64 == 0 and K % 64 == 0 and 1 <= splits <= K // 64, "bm / splits / alignment")
+    _req(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() >= N))
+    _req(x.ld >= K and y.ld >= N, "row stride")
+    if M > 0:
+        _req(_fits(x.t, _max_row(x, M) * x.ld + K) and _fits(y.t, _max_row(y, M) * y.ld + N), "storage bounds")
+    if resid is not None:
+        _req(resid.t.dtype == x.t.dtype and resid.ld >= N)
+        _req(M == 0 or _fits(resid.t, _max_row(resid, M) * resid.ld + N), "storage bounds")
+        r = [resid.t.data_ptr(), resid.ld, *resid.map()]
+    else:
+        r = [None, 0, 0, 0, 0]
+    if ln is not None:
+        _req(ln[0].dtype == ln[1].dtype == torch.float32 and ln[0].numel() >= 2 * M and ln[1].numel() >= N)
+    if part is not None:
+        _req(part.dtype == torch.float32 and part.is_contiguous())
+        _req(M == 0 or part.numel() >= (_max_row(y, M) + 1) * (N // 64) * 2, "storage bounds")
+    _req(_splitk_aligned(x, w, y, bias, resid, ln, part), "operand alignment")
+    need = gemm_splitk_ws_bytes(M, N, bm, splits)
+    if ws is None and need > 0:
+        ws = torch.empty(need // 4, dtype=torch.float32, device=y.t.device)
+    if ws is not None:
+        _req(ws.dtype == torch.float32 and ws.is_contiguous() and ws.numel() * 4 >= need, "workspace")
+    rc = lib().sdp_gemm_splitk(BF16, *x.args(), w.data_ptr(), w.stride(0), _ptr(bias), *r, *y.args(), M, N, K, act,
+                               int(bool(resid_pre)), _ptr(ln[0]) if ln else None, _ptr(ln[1]) if ln else None,
+                               _ptr(part), bm, splits, _ptr(ws), ws.numel() * 4 if ws is not None else 0,
+                               _stream(y.t))
+    _check(rc, "gemm_splitk")
 
 
 def layernorm(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, eps: float, y: Rows, M: int, C: int):
