@@ -31,7 +31,7 @@ import layers
 from layers import ConvMixer, EmbeddingLayer, ConvPatcher, Block, FinalBlock, ClassificationHead, ConvEmbedding  # noqa: F401
 from utility_layers import SdPModel, StochasticDepth  # noqa: F401
 from layers import new_partials  # token-buffer plumbing of the fused path
-from sdpnet_engine import act_code, as_dtype, cached, compute_dtype, hooked as _hooked
+from sdpnet_engine import act_code, as_dtype, cached, compute_dtype, geometry, hooked as _hooked, out_features
 from training_utilities import KeLu
 
 # torch.compile of a training model: "layer" (default) = one custom op per sub-layer (DDP's
@@ -219,11 +219,8 @@ class MainModel(SdPModel):
     def _fused_forward(self, x: torch.Tensor, num_registers: int, dt, return_raw_outputs: bool):
         # (also the body of the torch.compile custom ops, sdpnet_ops.main_forward[_raw])
         with torch.no_grad(), sp.low_latency(self._low_latency_on()):
-            B, _, Hi, Wi = x.shape
-            p = self.conv_init.patch_size
-            Hp, Wp = Hi // p, Wi // p
-            C = self.conv_init.conv.out_channels
-            ncls = self.output_head._prep(dt)["lin"][-1][0].shape[0]
+            B, _, Hp, Wp, _, C = geometry(self, x.shape, num_registers)
+            ncls = out_features(self)
             self._prepare(dt, Hp, Wp)
             x = x.contiguous()
             logits = torch.empty(B, ncls, dtype=dt, device=x.device)

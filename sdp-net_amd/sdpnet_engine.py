@@ -137,6 +137,29 @@ def num_reg_rows(max_num: int, num_registers: int) -> int:
     return len(range(max_num)[: num_registers + 1])
 
 
+def reg_rows(model: nn.Module, num_registers: int) -> int:
+    """Register rows R at the head of every image's token rows."""
+    emb = model.embedding_layer
+    conv_emb = not hasattr(emb, "horizontal_embedding_layer")
+    return num_reg_rows(emb.register.shape[0] if conv_emb else emb.max_num_registers, num_registers)
+
+
+def out_features(model: nn.Module) -> int:
+    """Width of the logits: the head's last Linear."""
+    return [m for m in model.output_head.output_head if isinstance(m, nn.Linear)][-1].out_features
+
+
+def geometry(model: nn.Module, image_shape, num_registers: int):
+    """(B, R, Hp, Wp, N, C) of a MainModel forward on an image batch of ``image_shape``: the patch
+    grid, the register rows and N = R + Hp*Wp token rows per image of width C.  Integer arithmetic
+    only, so the shapes may be Dynamo's symbolic ints (the custom ops' fakes)."""
+    B, _, Hi, Wi = image_shape
+    p = model.conv_init.patch_size
+    Hp, Wp = Hi // p, Wi // p
+    R = reg_rows(model, num_registers)
+    return B, R, Hp, Wp, R + Hp * Wp, model.conv_init.conv.out_channels
+
+
 def hooked(module: nn.Module) -> bool:
     """True if any submodule has forward (pre-)hooks: the caller then composes
     the forward module by module so every hooked __call__ fires."""

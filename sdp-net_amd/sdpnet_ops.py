@@ -25,7 +25,7 @@ from typing import Tuple
 import torch
 from torch import Tensor
 
-from sdpnet_engine import num_reg_rows
+from sdpnet_engine import geometry, out_features, reg_rows
 from typing import List, Optional
 
 _MODELS: "dict[int, weakref.ref]" = {}
@@ -50,21 +50,6 @@ def lookup(handle: int):
     return model
 
 
-def _register_rows(model, num_registers: int) -> int:
-    emb = model.embedding_layer
-    n = emb.register.shape[0] if hasattr(emb, "register") else emb.max_num_registers
-    return num_reg_rows(n, num_registers)
-
-
-def _shapes(model, x: Tensor, num_registers: int):
-    B, _, Hi, Wi = x.shape
-    p = model.conv_init.patch_size
-    C = model.conv_init.conv.out_channels
-    lins = [m for m in model.output_head.output_head if isinstance(m, torch.nn.Linear)]
-    ncls = lins[-1].out_features
-    return B, C, Hi // p, Wi // p, ncls, _register_rows(model, num_registers)
-
-
 @torch.library.custom_op("sdpnet::main_forward", mutates_args=(), device_types="cuda")
 def main_forward(x: Tensor, handle: int, num_registers: int, dtype_code: int) -> Tensor:
     return lookup(handle)._fused_forward(x, num_registers, _DTYPES[dtype_code], False)
@@ -72,8 +57,7 @@ def main_forward(x: Tensor, handle: int, num_registers: int, dtype_code: int) ->
 
 @main_forward.register_fake
 def _main_forward_fake(x, handle, num_registers, dtype_code):
-    B, C, Hp, Wp, ncls, R = _shapes(lookup(handle), x, num_registers)
-    return x.new_empty((B, ncls), dtype=_DTYPES[dtype_code])
+    return x.new_empty((x.shape[0], out_features(lookup(handle))), dtype=_DTYPES[dtype_code])
 
 
 @torch.library.custom_op("sdpnet::main_forward_raw", mutates_args=(), device_types="cuda")
@@ -84,9 +68,10 @@ def main_forward_raw(x: Tensor, handle: int, num_registers: int, dtype_code: int
 
 @main_forward_raw.register_fake
 def _main_forward_raw_fake(x, handle, num_registers, dtype_code):
-    B, C, Hp, Wp, ncls, R = _shapes(lookup(handle), x, num_registers)
+    model = lookup(handle)
+    B, R, Hp, Wp, _, C = geometry(model, x.shape, num_registers)
     dt = _DTYPES[dtype_code]
-    return (x.new_empty((B, ncls), dtype=dt), x.new_empty((B, C, Hp, Wp), dtype=dt),
+    return (x.new_empty((B, out_features(model)), dtype=dt), x.new_empty((B, C, Hp, Wp), dtype=dt),
             x.new_empty((B, R, C), dtype=dt))
 
 
@@ -103,44 +88,54 @@ def _main_forward_raw_fake(x, handle, num_registers, dtype_code):
 # called directly) and parks the tape in _TAPES under ``key``, a 1-element tensor that is
 # also a saved tensor of the autograd node: backward finds the tape by key.data_ptr() (no
 # host sync) and frees it; a tape whose key dies without a backward is dropped with it.
+# The per-layer and head-with-raw-outputs pairs below park their state the same way.
 # ---------------------------------------------------------------------------
-_TAPES: "dict[int, list]" = {}
+_TAPES: "dict[int, object]" = {}
 
 
-def _drop_tape(k: int):
-    _TAPES.pop(k, None)
+def _park(state, like: Tensor) -> Tensor:
+    """Keep a forward's state for its backward op; returns the key tensor (on ``like``'s device)."""
+    key = torch.empty(1, dtype=torch.int64, device=like.device)
+    _TAPES[key.data_ptr()] = state
+    weakref.finalize(key, _TAPES.pop, key.data_ptr(), None)
+    return key
+
+
+def _take(key: Tensor, what: str):
+    """The state parked under ``key``, handed out once."""
+    state = _TAPES.pop(key.data_ptr(), None)
+    if state is None:
+        raise RuntimeError(f"sdpnet: no saved training forward for {what} (backward run twice?)")
+    return state
+
+
+def _fake_grads(params):
+    return [torch.empty_like(p) for p in params]
 
 
 @torch.library.custom_op("sdpnet::train_forward", mutates_args=(), device_types="cuda")
 def train_forward(x: Tensor, params: List[Tensor], handle: int, num_registers: int,
                   dtype_code: int) -> Tuple[Tensor, Tensor]:
     import sdpnet_train
-    model = lookup(handle)
-    logits, tape = sdpnet_train.tape_forward(model, x, num_registers, _DTYPES[dtype_code])
-    key = torch.empty(1, dtype=torch.int64, device=x.device)
-    _TAPES[key.data_ptr()] = tape
-    weakref.finalize(key, _drop_tape, key.data_ptr())
-    return logits, key
+    logits, tape = sdpnet_train.tape_forward(lookup(handle), x, num_registers, _DTYPES[dtype_code])
+    return logits, _park(tape, x)
 
 
 @train_forward.register_fake
 def _train_forward_fake(x, params, handle, num_registers, dtype_code):
-    B, C, Hp, Wp, ncls, R = _shapes(lookup(handle), x, num_registers)
-    return x.new_empty((B, ncls), dtype=_DTYPES[dtype_code]), x.new_empty((1,), dtype=torch.int64)
+    return (x.new_empty((x.shape[0], out_features(lookup(handle))), dtype=_DTYPES[dtype_code]),
+            x.new_empty((1,), dtype=torch.int64))
 
 
 @torch.library.custom_op("sdpnet::train_backward", mutates_args=(), device_types="cuda")
 def train_backward(grad_logits: Tensor, key: Tensor, params: List[Tensor], handle: int) -> List[Tensor]:
     import sdpnet_train
-    tape = _TAPES.pop(key.data_ptr(), None)
-    if tape is None:
-        raise RuntimeError("sdpnet: no saved training forward for this backward (backward run twice?)")
-    return sdpnet_train.tape_backward(tape, grad_logits.contiguous(), params)
+    return sdpnet_train.tape_backward(_take(key, "this backward"), grad_logits.contiguous(), params)
 
 
 @train_backward.register_fake
 def _train_backward_fake(grad_logits, key, params, handle):
-    return [torch.empty_like(p) for p in params]
+    return _fake_grads(params)
 
 
 def _train_setup_context(ctx, inputs, output):
@@ -178,10 +173,7 @@ def train_layer(t: Tensor, params: List[Tensor], handle: int, layer: int, num_re
     import sdpnet_train
     out, rec = sdpnet_train.layer_forward(lookup(handle), layer, t, num_registers, _DTYPES[dtype_code],
                                           need_dx=bool(need_dx))
-    key = torch.empty(1, dtype=torch.int64, device=t.device)
-    _TAPES[key.data_ptr()] = rec
-    weakref.finalize(key, _drop_tape, key.data_ptr())
-    return out, key
+    return out, _park(rec, t)
 
 
 @train_layer.register_fake
@@ -192,11 +184,10 @@ def _train_layer_fake(t, params, handle, layer, num_registers, dtype_code, batch
     key = t.new_empty((1,), dtype=torch.int64)
     dt = _DTYPES[dtype_code]
     if kind == "embed":
-        B, C, Hp, Wp, ncls, R = _shapes(model, t, num_registers)
-        return t.new_empty((B * (R + Hp * Wp), C), dtype=sdpnet_train.stream_dtype(dt, C)), key
+        B, _, _, _, N, C = geometry(model, t.shape, num_registers)
+        return t.new_empty((B * N, C), dtype=sdpnet_train.stream_dtype(dt, C)), key
     if kind == "head":
-        lins = [m for m in model.output_head.output_head if isinstance(m, torch.nn.Linear)]
-        return t.new_empty((batch, lins[-1].out_features), dtype=dt), key
+        return t.new_empty((batch, out_features(model)), dtype=dt), key
     return torch.empty_like(t), key
 
 
@@ -204,10 +195,7 @@ def _train_layer_fake(t, params, handle, layer, num_registers, dtype_code, batch
 def train_layer_backward(grad_out: Tensor, key: Tensor, params: List[Tensor], handle: int, layer: int,
                          in_shape: List[int], in_dtype: int) -> Tuple[Tensor, List[Tensor]]:
     import sdpnet_train
-    rec = _TAPES.pop(key.data_ptr(), None)
-    if rec is None:
-        raise RuntimeError("sdpnet: no saved training forward for this layer's backward (backward run twice?)")
-    gin, grads = sdpnet_train.layer_backward(rec, grad_out)
+    gin, grads = sdpnet_train.layer_backward(_take(key, "this layer's backward"), grad_out)
     if gin is None:  # layer 0 with an image that needs no gradient
         gin = grad_out.new_empty((0,))
     return gin, grads
@@ -224,7 +212,7 @@ def _train_layer_backward_fake(grad_out, key, params, handle, layer, in_shape, i
     # itself is not kept alive for the backward (eager frees it once the layer's ctx is done with it).
     # Layer 0 records an empty shape when the image needs no gradient.
     gin = grad_out.new_empty(in_shape, dtype=_GRAD_DTYPES[in_dtype]) if in_shape else grad_out.new_empty((0,))
-    return gin, [torch.empty_like(p) for p in params]
+    return gin, _fake_grads(params)
 
 
 def _layer_setup_context(ctx, inputs, output):
@@ -260,22 +248,18 @@ def train_head_raw(t: Tensor, params: List[Tensor], handle: int, layer: int, num
     import sdpnet_train
     model = lookup(handle)
     C = model.conv_init.conv.out_channels
-    geo = (batch, _register_rows(model, num_registers), hp, wp, C)
+    geo = (batch, reg_rows(model, num_registers), hp, wp, C)
     xo, regs = sdpnet_train.raw_outputs(t, geo)
     logits, rec = sdpnet_train.layer_forward(model, layer, t, num_registers, _DTYPES[dtype_code])
-    key = torch.empty(1, dtype=torch.int64, device=t.device)
-    _TAPES[key.data_ptr()] = (rec, geo)
-    weakref.finalize(key, _drop_tape, key.data_ptr())
-    return logits, xo, regs, key
+    return logits, xo, regs, _park((rec, geo), t)
 
 
 @train_head_raw.register_fake
 def _train_head_raw_fake(t, params, handle, layer, num_registers, dtype_code, batch, hp, wp):
     model = lookup(handle)
-    lins = [m for m in model.output_head.output_head if isinstance(m, torch.nn.Linear)]
     C = model.conv_init.conv.out_channels
-    R = _register_rows(model, num_registers)
-    return (t.new_empty((batch, lins[-1].out_features), dtype=_DTYPES[dtype_code]),
+    R = reg_rows(model, num_registers)
+    return (t.new_empty((batch, out_features(model)), dtype=_DTYPES[dtype_code]),
             t.new_empty((batch, C, hp, wp)), t.new_empty((batch, R, C)), t.new_empty((1,), dtype=torch.int64))
 
 
@@ -284,17 +268,14 @@ def train_head_raw_backward(grad_logits: Tensor, grad_xo: Optional[Tensor], grad
                             params: List[Tensor], handle: int, in_shape: List[int],
                             in_dtype: int) -> Tuple[Tensor, List[Tensor]]:
     import sdpnet_train
-    tape = _TAPES.pop(key.data_ptr(), None)
-    if tape is None:
-        raise RuntimeError("sdpnet: no saved training forward for the head's backward (backward run twice?)")
-    rec, geo = tape
+    rec, geo = _take(key, "the head's backward")
     gin, grads = sdpnet_train.layer_backward(rec, grad_logits)
     return sdpnet_train.add_raw_output_grads(gin, grad_xo, grad_regs, geo), grads
 
 
 @train_head_raw_backward.register_fake
 def _train_head_raw_backward_fake(grad_logits, grad_xo, grad_regs, key, params, handle, in_shape, in_dtype):
-    return grad_logits.new_empty(in_shape, dtype=_GRAD_DTYPES[in_dtype]), [torch.empty_like(p) for p in params]
+    return grad_logits.new_empty(in_shape, dtype=_GRAD_DTYPES[in_dtype]), _fake_grads(params)
 
 
 def _head_raw_setup_context(ctx, inputs, output):

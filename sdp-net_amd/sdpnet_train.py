@@ -43,16 +43,17 @@ gradient is rounded to bf16 only where it enters a branch (``stream_dtype``;
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 import struct
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
 import sdpnet_hip as sp
-from sdpnet_engine import act_code, as_dtype, compute_dtype, f32, num_reg_rows
+from sdpnet_engine import act_code, as_dtype, compute_dtype, f32, geometry
 
 Rows = sp.Rows
 
@@ -175,11 +176,22 @@ def _dgrad_act(dy: torch.Tensor, w: torch.Tensor, z: torch.Tensor, act: int, p: 
 # Per-step weight preparation: the bf16 GEMM operands of every ConvMixer / EncoderLayer weight
 # (forward) and their transposes (input-gradient GEMMs) from the fp32 parameters, in ONE
 # sdp_mt_cast_transpose launch at the start of a bf16 training forward, into buffers kept on
-# the model.  Only valid inside that forward (_WPREP is cleared after it), so a sub-module
-# trained on its own or an fp32 forward never sees them.
+# the model.  Only valid inside that forward (``with _wprep_valid(...)`` clears _WPREP on every
+# exit), so a sub-module trained on its own or an fp32 forward never sees them.
 # ---------------------------------------------------------------------------
 _WPREP: Optional[dict] = None
 _WPREP_ON = os.environ.get("SDPNET_WEIGHT_PREP", "1") != "0"
+
+
+@contextlib.contextmanager
+def _wprep_valid(bufs: Optional[dict]):
+    """The prepared weights ``bufs`` (what _prep_weights returned) are _WPREP inside this block only."""
+    global _WPREP
+    _WPREP = bufs
+    try:
+        yield
+    finally:
+        _WPREP = None
 
 
 def _weight_jobs(model):
@@ -956,6 +968,105 @@ class _RawOutFn(torch.autograd.Function):
 
 
 # ---------------------------------------------------------------------------
+# The plan of a training forward: its geometry and its sub-layers in execution order, each a
+# _Step that says which Function runs on which module with which arguments.  _plan is the one
+# description of MainModel's training walk; the eager forward (train_forward), the tape
+# (tape_forward) and the per-layer ops (layer_forward) are three short drivers over it, so they
+# cannot drift apart.  Block.forward on its own (train_block) builds its steps the same way.
+# ---------------------------------------------------------------------------
+def _pos_tables(emb):
+    """(Eh, Ew) of an EmbeddingLayer; (None, None) for a ConvEmbedding (its bone table is pooled)."""
+    if not hasattr(emb, "horizontal_embedding_layer"):
+        return None, None
+    return emb.horizontal_embedding_layer.weight, emb.vertical_embedding_layer.weight
+
+
+def _embed_params(model) -> List[Optional[nn.Parameter]]:
+    return [model.conv_init.conv.weight, *_pos_tables(model.embedding_layer),
+            model.embedding_layer.register_embedding_layer.weight]
+
+
+# kind -> (Function, takes the forward's rng, parameter list of its module with the Nones)
+_KINDS = {"embed": (_EmbedFn, False, _embed_params), "mixer": (_MixerFn, False, _mixer_params),
+          "enc": (_EncoderFn, True, _enc_params), "head": (_HeadFn, True, _head_params)}
+
+
+class _Step(NamedTuple):
+    kind: str     # embed / mixer / enc / head
+    fn: type      # its autograd Function
+    lead: int     # inputs of fn before the parameters: tok, geo, mod, dt (+ rng)
+    mod: nn.Module
+    geo: tuple
+    rng: bool
+    params: list
+
+    def args(self, tok, dt, rng):
+        return (tok, self.geo, self.mod, dt, *((rng,) if self.rng else ()), *self.params)
+
+
+class _Plan(NamedTuple):
+    B: int
+    R: int
+    Hp: int
+    Wp: int
+    N: int
+    C: int
+    dt: torch.dtype
+    sdt: torch.dtype  # of the residual stream
+    steps: List[_Step]
+
+
+def _enc_geo(e, B: int, N: int, mask):
+    """(B, N) or (B, N, (bias, batch stride, head stride)): a mask takes the materialised attention
+    (layers.py:289-298: SDPA attn_mask semantics for fast_att, masked_fill(mask == 0, -inf) for the
+    manual path, via EncoderLayer._mask_bias as in eval)."""
+    if mask is None:
+        return (B, N)
+    return (B, N, e._mask_bias(mask, B, N))
+
+
+def _block_layers(blk):
+    """(kind, module) of a Block's sub-layers in execution order (layers.py:381-386)."""
+    mx = [("mixer", m) for m in blk.conv_blocks]
+    en = [("enc", blk.t_block)]
+    return mx + en if blk.conv_first else en + mx
+
+
+def _steps(layers, B, R, Hp, Wp, C, num_registers=None, sdt=None, mask=None) -> List[_Step]:
+    N = R + Hp * Wp
+    geos = {"embed": (B, R, Hp, Wp, num_registers, sdt), "mixer": (B, R, Hp, Wp), "head": (B, R, Hp * Wp, N, C)}
+    out = []
+    for kind, mod in layers:
+        fn, rng, params = _KINDS[kind]
+        geo = _enc_geo(mod, B, N, mask) if kind == "enc" else geos[kind]
+        out.append(_Step(kind, fn, 4 + rng, mod, geo, rng, params(mod)))
+    return out
+
+
+def train_layers(model):
+    """The sub-layers of a training forward in execution order: (kind, module)."""
+    out = [("embed", model)]
+    for blk in model.blocks:                                           # model.py:139-140
+        out += _block_layers(blk)
+    return out + [("enc", model.final_block.t_block), ("head", model.output_head)]  # model.py:143, :146
+
+
+def layer_params(model, kind: str, mod) -> List[Optional[nn.Parameter]]:
+    return _KINDS[kind][2](mod)
+
+
+def _plan(model, image_shape, num_registers: int, dt) -> _Plan:
+    """Geometry and steps of MainModel's training forward on images of ``image_shape`` (pure: no
+    kernel, no random draw)."""
+    B, R, Hp, Wp, N, C = geometry(model, image_shape, num_registers)
+    eh, ew = _pos_tables(model.embedding_layer)
+    if eh is not None and (Hp > eh.shape[0] or Wp > ew.shape[0]):
+        raise RuntimeError(f"image grid {Hp}x{Wp} exceeds max_image_size {[ew.shape[0], eh.shape[0]]}")
+    sdt = stream_dtype(dt, C)
+    return _Plan(B, R, Hp, Wp, N, C, dt, sdt, _steps(train_layers(model), B, R, Hp, Wp, C, num_registers, sdt))
+
+
+# ---------------------------------------------------------------------------
 # Sub-module forwards in training mode (Block(...)(x, reg), EncoderLayer, ConvMixer, the
 # head, the LayerNorm / patcher / embedding leaves): the same per-sub-layer Functions on a
 # token buffer built from (x NCHW, registers), with differentiable layout changes either side.
@@ -999,15 +1110,6 @@ class _ToTokFn(torch.autograd.Function):
         return dx, dreg, None
 
 
-def _enc_geo(e, B: int, N: int, mask):
-    """(B, N) or (B, N, (bias, batch stride, head stride)): a mask takes the materialised attention
-    (layers.py:289-298: SDPA attn_mask semantics for fast_att, masked_fill(mask == 0, -inf) for the
-    manual path, via EncoderLayer._mask_bias as in eval)."""
-    if mask is None:
-        return (B, N)
-    return (B, N, e._mask_bias(mask, B, N))
-
-
 def train_conv_mixer(m, x: torch.Tensor) -> torch.Tensor:
     """ConvMixer.forward in train mode (layers.py:83-104): x [B, C, H, W] -> x."""
     dt = compute_dtype(x, m)
@@ -1033,17 +1135,8 @@ def train_block(blk, x: torch.Tensor, reg: torch.Tensor, mask=None):
     R = reg.shape[1]
     tok = _ToTokFn.apply(x, reg, stream_dtype(dt, C))
     rng = _RNG()
-
-    def mixers(t):
-        for mx in blk.conv_blocks:
-            t = _MixerFn.apply(t, (B, R, H, W), mx, dt, *_mixer_params(mx))
-        return t
-
-    def enc(t):
-        return _EncoderFn.apply(t, _enc_geo(blk.t_block, B, R + H * W, mask), blk.t_block, dt, rng,
-                                *_enc_params(blk.t_block))
-
-    tok = enc(mixers(tok)) if blk.conv_first else mixers(enc(tok))
+    for st in _steps(_block_layers(blk), B, R, H, W, C, mask=mask):
+        tok = st.fn.apply(*st.args(tok, dt, rng))
     return _RawOutFn.apply(tok, (B, R, H, W, C))
 
 
@@ -1212,10 +1305,8 @@ class _PosEmbFn(torch.autograd.Function):
 
 def train_pos_embedding(emb, x: torch.Tensor, num_registers: int):
     compute_dtype(x, emb)
-    conv_emb = not hasattr(emb, "horizontal_embedding_layer")
-    eh = None if conv_emb else emb.horizontal_embedding_layer.weight
-    ew = None if conv_emb else emb.vertical_embedding_layer.weight
-    bone = emb.bone if conv_emb and isinstance(emb.bone, nn.Parameter) else None
+    eh, ew = _pos_tables(emb)
+    bone = emb.bone if eh is None and isinstance(emb.bone, nn.Parameter) else None
     return _PosEmbFn.apply(x, emb, num_registers, eh, ew, bone, emb.register_embedding_layer.weight)
 
 
@@ -1234,126 +1325,54 @@ def eval_forward(model, x: torch.Tensor, num_registers: int = 3, return_raw_outp
 
 
 def train_forward(model, x: torch.Tensor, num_registers: int = 3, return_raw_outputs: bool = False):
-    """MainModel.forward in training mode (model.py:129-149 with dropout / drop path active)."""
-    global _WPREP
-    _WPREP = _prep_weights(model, compute_dtype(x, model))
-    try:
-        return _train_forward(model, x, num_registers, return_raw_outputs)
-    finally:
-        _WPREP = None
-
-
-def _train_forward(model, x: torch.Tensor, num_registers: int, return_raw_outputs: bool):
+    """MainModel.forward in training mode (model.py:129-149 with dropout / drop path active): the
+    plan's steps as a chain of autograd Functions."""
     dt = compute_dtype(x, model)
-    B, _, Hi, Wi = x.shape
-    p = model.conv_init.patch_size
-    Hp, Wp = Hi // p, Wi // p
-    emb = model.embedding_layer
-    conv_emb = not hasattr(emb, "horizontal_embedding_layer")
-    if conv_emb:
-        R = num_reg_rows(emb.register.shape[0], num_registers)
-        eh = ew = None
-    else:
-        R = num_reg_rows(emb.max_num_registers, num_registers)
-        eh, ew = emb.horizontal_embedding_layer.weight, emb.vertical_embedding_layer.weight
-        if Hp > eh.shape[0] or Wp > ew.shape[0]:
-            raise RuntimeError(f"image grid {Hp}x{Wp} exceeds max_image_size {[ew.shape[0], eh.shape[0]]}")
-    N = R + Hp * Wp
-    C = model.conv_init.conv.out_channels
-    rng = _RNG()
-    # the image goes in as is (patchify converts to the compute dtype), so a gradient reaches it
-    tok = _EmbedFn.apply(x, (B, R, Hp, Wp, num_registers, stream_dtype(dt, C)), model, dt, model.conv_init.conv.weight, eh, ew,
-                         emb.register_embedding_layer.weight)
-
-    def enc(t, e):
-        return _EncoderFn.apply(t, (B, N), e, dt, rng, *_enc_params(e))
-
-    def mixers(t, blk):
-        for mx in blk.conv_blocks:
-            t = _MixerFn.apply(t, (B, R, Hp, Wp), mx, dt, *_mixer_params(mx))
-        return t
-
-    for blk in model.blocks:                                           # model.py:139-140, layers.py:381-386
-        if blk.conv_first:
-            tok = enc(mixers(tok, blk), blk.t_block)
-        else:
-            tok = mixers(enc(tok, blk.t_block), blk)
-    tok = enc(tok, model.final_block.t_block)                          # model.py:143
-    head = model.output_head
-    logits = _HeadFn.apply(tok, (B, R, Hp * Wp, N, C), head, dt, rng, *_head_params(head))
-    if not return_raw_outputs:
-        return logits
-    xo, regs = _RawOutFn.apply(tok, (B, R, Hp, Wp, C))
-    return logits, xo, regs
+    with _wprep_valid(_prep_weights(model, dt)):
+        plan = _plan(model, x.shape, num_registers, dt)  # host work, under the weight preparation's kernel
+        rng = _RNG()
+        tok = x  # the image goes in as is (patchify converts to the compute dtype), so a gradient reaches it
+        for st in plan.steps[:-1]:
+            tok = st.fn.apply(*st.args(tok, dt, rng))
+        logits = plan.steps[-1].fn.apply(*plan.steps[-1].args(tok, dt, rng))
+        if not return_raw_outputs:
+            return logits
+        xo, regs = _RawOutFn.apply(tok, (plan.B, plan.R, plan.Hp, plan.Wp, plan.C))
+        return logits, xo, regs
 
 
 # ---------------------------------------------------------------------------
-# The same training forward / backward as an explicit tape (torch.compile path)
+# The same plan without autograd (torch.compile paths): every step's Function.forward is called
+# directly on a stand-in ctx, and (fn, ctx, lead, params) is the record its backward replays.
 # ---------------------------------------------------------------------------
 class _Ctx:
     """Stand-in for an autograd ctx: the Functions above keep their state in plain attributes."""
 
 
+def _record(st: _Step, ctx: _Ctx, tok: torch.Tensor, dt, rng):
+    return st.fn.forward(ctx, *st.args(tok, dt, rng)), (st.fn, ctx, st.lead, st.params)
+
+
+def _param_grad(prm: torch.Tensor, gp: Optional[torch.Tensor]) -> torch.Tensor:
+    """A backward's gradient ``gp`` in the shape and dtype of ``prm`` (zeros for None), never a view
+    (e.g. the q/k/v slices of one fused dW): the outputs of an op may not alias."""
+    t = gp.reshape(prm.shape).to(prm.dtype) if gp is not None else torch.zeros_like(prm)
+    return t.clone() if t._base is not None else t
+
+
 def tape_forward(model, x: torch.Tensor, num_registers: int, dt):
-    """train_forward with every sub-layer Function's forward called directly and its ctx
-    kept on a tape (no autograd graph), for the opaque torch.compile custom op
-    (sdpnet_ops.train_forward).  Same kernels, same order, same RNG draws as train_forward,
-    so a compiled step is bit-identical to an eager one."""
-    global _WPREP
-    _WPREP = _prep_weights(model, dt)
-    try:
-        return _tape_forward(model, x, num_registers, dt)
-    finally:
-        _WPREP = None
-
-
-def _tape_forward(model, x: torch.Tensor, num_registers: int, dt):
-    B, _, Hi, Wi = x.shape
-    p = model.conv_init.patch_size
-    Hp, Wp = Hi // p, Wi // p
-    emb = model.embedding_layer
-    conv_emb = not hasattr(emb, "horizontal_embedding_layer")
-    if conv_emb:
-        R = num_reg_rows(emb.register.shape[0], num_registers)
-        eh = ew = None
-    else:
-        R = num_reg_rows(emb.max_num_registers, num_registers)
-        eh, ew = emb.horizontal_embedding_layer.weight, emb.vertical_embedding_layer.weight
-        if Hp > eh.shape[0] or Wp > ew.shape[0]:
-            raise RuntimeError(f"image grid {Hp}x{Wp} exceeds max_image_size {[ew.shape[0], eh.shape[0]]}")
-    N = R + Hp * Wp
-    C = model.conv_init.conv.out_channels
-    rng = _RNG()
+    """The plan's steps with every record kept on a tape, for the opaque torch.compile custom op
+    (sdpnet_ops.train_forward).  Same kernels, same order, same RNG draws as train_forward, so a
+    compiled step is bit-identical to an eager one.  No ctx asks for the image gradient."""
     tape = []
-
-    def run(fn, lead, params, *args):
-        ctx = _Ctx()
-        out = fn.forward(ctx, *args, *params)
-        tape.append((fn, ctx, lead, params))
-        return out
-
-    xin = x if x.dtype == dt else as_dtype(x, dt)
-    with torch.no_grad():
-        tok = run(_EmbedFn, 4, [model.conv_init.conv.weight, eh, ew, emb.register_embedding_layer.weight],
-                  xin, (B, R, Hp, Wp, num_registers, stream_dtype(dt, C)), model, dt)
-
-        def enc(t, e):
-            return run(_EncoderFn, 5, _enc_params(e), t, (B, N), e, dt, rng)
-
-        def mixers(t, blk):
-            for mx in blk.conv_blocks:
-                t = run(_MixerFn, 4, _mixer_params(mx), t, (B, R, Hp, Wp), mx, dt)
-            return t
-
-        for blk in model.blocks:
-            if blk.conv_first:
-                tok = enc(mixers(tok, blk), blk.t_block)
-            else:
-                tok = mixers(enc(tok, blk.t_block), blk)
-        tok = enc(tok, model.final_block.t_block)
-        head = model.output_head
-        logits = run(_HeadFn, 5, _head_params(head), tok, (B, R, Hp * Wp, N, C), head, dt, rng)
-    return logits, tape
+    with _wprep_valid(_prep_weights(model, dt)), torch.no_grad():
+        plan = _plan(model, x.shape, num_registers, dt)
+        rng = _RNG()
+        tok = x if x.dtype == dt else as_dtype(x, dt)
+        for st in plan.steps:
+            tok, rec = _record(st, _Ctx(), tok, dt, rng)
+            tape.append(rec)
+    return tok, tape
 
 
 def tape_backward(tape, dlogits: torch.Tensor, params: List[torch.Tensor]) -> List[torch.Tensor]:
@@ -1369,13 +1388,7 @@ def tape_backward(tape, dlogits: torch.Tensor, params: List[torch.Tensor]) -> Li
                 if prm is not None and gp is not None:
                     grads[id(prm)] = gp if id(prm) not in grads else grads[id(prm)] + gp
     tape.clear()
-    out = []
-    for q in params:
-        t = grads[id(q)].reshape(q.shape).to(q.dtype) if id(q) in grads else torch.zeros_like(q)
-        if t._base is not None:  # e.g. the q/k/v slices of one fused dW: the op's outputs may not alias
-            t = t.clone()
-        out.append(t)
-    return out
+    return [_param_grad(q, grads.get(id(q))) for q in params]
 
 
 # ---------------------------------------------------------------------------
@@ -1384,103 +1397,41 @@ def tape_backward(tape, dlogits: torch.Tensor, params: List[torch.Tensor]) -> Li
 # formula, so a compiled backward is a chain of per-layer ops and DDP's bucket hooks (and
 # Dynamo's DDPOptimizer graph splits) see each layer's gradients as soon as its backward op
 # returns -- the overlap the eager Functions give (training_tools.py:36-39 compiles DDP(model)).
-# The forward session (seed source, prepared bf16 weights, geometry) lives on the model between
-# the first and the last layer op of one forward; same Functions, same kernels, same RNG draws
-# in the same order as train_forward, so the compiled step is bit-identical to the eager one.
+# The forward session (the plan, seed source, prepared bf16 weights) lives on the model between
+# the first and the last layer op of one forward; layer i runs plan.steps[i], so the compiled
+# step is bit-identical to the eager one.
 # ---------------------------------------------------------------------------
-def train_layers(model):
-    """The sub-layers of a training forward in execution order: (kind, module)."""
-    out = [("embed", model)]
-    for blk in model.blocks:                                           # model.py:139-140
-        mx = [("mixer", m) for m in blk.conv_blocks]
-        en = [("enc", blk.t_block)]
-        out += (mx + en) if blk.conv_first else (en + mx)
-    out += [("enc", model.final_block.t_block), ("head", model.output_head)]
-    return out
-
-
-def layer_params(model, kind: str, mod) -> List[Optional[nn.Parameter]]:
-    if kind == "embed":
-        emb = model.embedding_layer
-        conv_emb = not hasattr(emb, "horizontal_embedding_layer")
-        eh = None if conv_emb else emb.horizontal_embedding_layer.weight
-        ew = None if conv_emb else emb.vertical_embedding_layer.weight
-        return [model.conv_init.conv.weight, eh, ew, emb.register_embedding_layer.weight]
-    if kind == "mixer":
-        return _mixer_params(mod)
-    if kind == "enc":
-        return _enc_params(mod)
-    return _head_params(mod)
-
-
 class _Session:
     pass
 
 
 def layer_forward(model, layer: int, t: torch.Tensor, num_registers: int, dt, need_dx: bool = False):
-    """Forward of sub-layer ``layer`` (train_layers order) with its ctx returned for the
+    """Forward of sub-layer ``layer`` (train_layers order) with its record returned for the
     backward op.  Layer 0 takes the image and opens the session, the last layer closes it;
     need_dx: the image requires grad (layer 0 then keeps what its input gradient needs)."""
-    global _WPREP
-    kind, mod = train_layers(model)[layer]
-    params = layer_params(model, kind, mod)
+    if layer == 0:
+        model._sdp_session = None  # a failed layer 0 leaves no session behind
+        S = _Session()
+        S.plan = _plan(model, t.shape, num_registers, dt)
+        S.wprep = _prep_weights(model, dt)  # kept for the later layers; _WPREP only inside a layer op
+        S.rng = _RNG()
+        model._sdp_session = S
+    else:
+        S = getattr(model, "_sdp_session", None)
+        if S is None:
+            raise RuntimeError("sdpnet: training layer op run outside a forward (layer 0 opens it)")
+    st = S.plan.steps[layer]
     ctx = _Ctx()
     ctx.needs_input_grad = (bool(need_dx),)
-    if kind == "embed":
-        S = _Session()
-        B, _, Hi, Wi = t.shape
-        p = model.conv_init.patch_size
-        Hp, Wp = Hi // p, Wi // p
-        emb = model.embedding_layer
-        conv_emb = not hasattr(emb, "horizontal_embedding_layer")
-        R = num_reg_rows(emb.register.shape[0] if conv_emb else emb.max_num_registers, num_registers)
-        if not conv_emb:
-            eh, ew = emb.horizontal_embedding_layer.weight, emb.vertical_embedding_layer.weight
-            if Hp > eh.shape[0] or Wp > ew.shape[0]:
-                raise RuntimeError(f"image grid {Hp}x{Wp} exceeds max_image_size {[ew.shape[0], eh.shape[0]]}")
-        S.geo = (B, R, Hp, Wp, Hp * Wp + R, model.conv_init.conv.out_channels)
-        S.dt = dt
-        # _WPREP is valid only inside one layer op (cleared on every exit, as for the other layers);
-        # the session keeps the prepared weights for the later layers, and a failed layer 0 leaves
-        # no session behind
-        try:
-            _WPREP = _prep_weights(model, dt)
-            S.wprep = _WPREP
-            S.rng = _RNG()
-            model._sdp_session = S
-            C = S.geo[5]
-            xin = t if t.dtype == dt else as_dtype(t, dt)
-            with torch.no_grad():
-                out = _EmbedFn.forward(ctx, xin, (B, R, Hp, Wp, num_registers, stream_dtype(dt, C)), model, dt,
-                                       *params)
-        except BaseException:
-            model._sdp_session = None
-            raise
-        finally:
-            _WPREP = None
-        return out, (_EmbedFn, ctx, 4, params)
-    S = getattr(model, "_sdp_session", None)
-    if S is None:
-        raise RuntimeError("sdpnet: training layer op run outside a forward (layer 0 opens it)")
-    B, R, Hp, Wp, N, C = S.geo
-    _WPREP = S.wprep
     try:
-        with torch.no_grad():
-            if kind == "mixer":
-                out = _MixerFn.forward(ctx, t, (B, R, Hp, Wp), mod, S.dt, *params)
-                rec = (_MixerFn, ctx, 4, params)
-            elif kind == "enc":
-                out = _EncoderFn.forward(ctx, t, (B, N), mod, S.dt, S.rng, *params)
-                rec = (_EncoderFn, ctx, 5, params)
-            else:
-                out = _HeadFn.forward(ctx, t, (B, R, Hp * Wp, N, C), mod, S.dt, S.rng, *params)
-                rec = (_HeadFn, ctx, 5, params)
+        with _wprep_valid(S.wprep), torch.no_grad():
+            if layer == 0 and t.dtype != S.plan.dt:
+                t = as_dtype(t, S.plan.dt)
+            out, rec = _record(st, ctx, t, S.plan.dt, S.rng)
     except BaseException:
         model._sdp_session = None  # an aborted forward closes the session (no stale weight copies)
         raise
-    finally:
-        _WPREP = None
-    if kind == "head":
+    if st.kind == "head":
         model._sdp_session = None
     return out, rec
 
@@ -1490,15 +1441,8 @@ def layer_backward(rec, g: torch.Tensor):
     fn, ctx, lead, params = rec
     with torch.no_grad():
         outs = fn.backward(ctx, g.contiguous())
-    grads = []
-    for prm, gp in zip(params, outs[lead:]):
-        if prm is None:
-            continue
-        t = gp.reshape(prm.shape).to(prm.dtype) if gp is not None else torch.zeros_like(prm)
-        if t._base is not None:  # e.g. the q/k/v slices of one fused dW: op outputs may not alias
-            t = t.clone()
-        grads.append(t)
-    return outs[0], grads  # layer 0: the image gradient, or None when the image needs none
+    # layer 0: outs[0] is the image gradient, or None when the image needs none
+    return outs[0], [_param_grad(prm, gp) for prm, gp in zip(params, outs[lead:]) if prm is not None]
 
 
 def raw_outputs(tok: torch.Tensor, geo):

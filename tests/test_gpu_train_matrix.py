@@ -155,8 +155,9 @@ def test_bf16_gradients_within_four_times_autocast(name, calls):
 def test_tape_gradients_equal_eager_bit_for_bit():
     """s_base in fp32 through sdpnet_train.tape_forward / tape_backward (the torch.compile custom
     op's body).  The tape calls the same autograd Functions' forward and backward directly, in
-    the same order, with the same arguments and the same seed draws (sdpnet_train._tape_forward
-    mirrors _train_forward line for line; every reduction is ordered, the side stream changes
+    the same order, with the same arguments and the same seed draws (sdpnet_train.tape_forward
+    is the same plan, sdpnet_train._plan, driven by Function.forward where train_forward drives it
+    by Function.apply; every reduction is ordered, the side stream changes
     timing only), so its gradients equal the eager ones bit for bit -- and therefore pass the fp32
     rule against the oracle, which is asserted as well."""
     import sdpnet_train
