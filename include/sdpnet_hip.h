@@ -50,6 +50,23 @@
  *                      dropout(P) (normalised by the saved LSE) for dV, dS = P o (dP - D) for dQ
  *                      and dK, with D = rowsum(dO o O) of the stored bf16 O; the outputs dQ,
  *                      dK, dV.  LSE and D are fp32.
+ *       sdp_gemm_mx:   operands as stored (MX, below), products and sums fp32 inside the scaled
+ *                      MFMA; bf16 output once, bf16(act(acc + b [+ R]) [+ R]) (fast GEMM 9's model);
+ *                      MX output: the fp32 act(acc + b) quantised by the MX rules, no bf16 in between.
+ *   - MX operand format (opt-in FP8 inference: sdp_mx_quant_rows, sdp_gemm_mx).
+ *       Elements: OCP e4m3fn bytes Q[rows][K], row stride in bytes, a multiple of 16.
+ *       Scales:   E8M0 bytes S[rows][K / 32], value 2^(code - 127): one scale per 32 consecutive K
+ *                 elements of one row.  K % 128 == 0.  Row stride in bytes, a multiple of 4.
+ *       Scale rule (nothing is clamped): amax = max |v| over the block = m 2^E with m in [1, 2), E
+ *                 read from the fp32 exponent bits (no log2f); e = E - 8 if m <= 1.75, else E - 7:
+ *                 the smallest exponent with amax 2^-e <= 448.  code = clamp(e + 127, 0, 254); the
+ *                 elements use the clamped code.  An all-zero block stores code 127 and zeros.
+ *       Element rule: v 2^-e is exact in fp32 and is rounded to nearest even on the e4m3 grid,
+ *                 subnormals (spacing 2^-9) included; it never saturates.  The sign is kept, also
+ *                 on a zero (-0.0 stores 0x80).
+ *       Non-finite input: a block that holds a NaN or +-Inf stores code 127 and the e4m3 NaN byte
+ *                 0x7f in all its 32 elements, so every GEMM output that consumes the block is NaN
+ *                 and no other row is touched.  (Scale code 255 is never written.)
  */
 #ifndef SDPNET_HIP_H
 #define SDPNET_HIP_H
@@ -132,6 +149,37 @@ int sdp_gemm_splitk(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_
 /* Workspace bytes of sdp_gemm_splitk: splits * M * N * 4 for splits > 1, else 0; -1 for
  * invalid arguments. */
 int64_t sdp_gemm_splitk_ws_bytes(int M, int N, int bm, int splits);
+/*
+ * MXFP8 inference (opt-in: sdp_gemm / sdp_gemm_ln never take it; "MX operand format" above).
+ * sdp_mx_quant_rows: the M logical rows of X (dtype 0 fp32 / 1 bf16, row map, 16-byte aligned rows)
+ * -> Q [M][K] e4m3 bytes (row stride ldq bytes) and S [M][K / 32] E8M0 bytes (row stride lds
+ * bytes), both dense, in one streaming pass.  stats != NULL ([M][2]: mean, rstd of logical row m)
+ * quantises the LayerNorm without affine, t = (float(x) - mean) * rstd as exactly those two fp32
+ * operations.  Also the weight quantiser (fp32 in, no stats).
+ * sdp_gemm_mx: Y = epilogue(Xq . Wq^T) on v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulation in a
+ * fixed K order (results depend on neither M nor the batch), any M >= 1 (clamped loads, masked
+ * stores).  Epilogue as sdp_gemm_ln without the LN fold: bias, act (codes 0-7; GELU in the fast
+ * GEMM's tanh form unless sdp_gemm_set_exact_gelu(1)), R with its row map and resid_pre, output
+ * row map, part ({mean, M2} of the stored bf16 row's 64-column chunks, layout as sdp_gemm_ln;
+ * N % 64 == 0).  Exactly one output: Y (bf16, row map) or Yq + Ys (MX: e4m3 bytes [M][N] and
+ * scales [M][N / 32] of the fp32 epilogue values, blocks along N, dense rows; no R, no part).
+ * Returns hipErrorInvalidValue before any launch when sdp_gemm_mx_applies is 0, an operand or a
+ * scale pointer is NULL, both or neither output is given, MX output comes with R or part, or an
+ * operand misses its alignment (Xq, Wq: 16-byte rows; scales: 4-byte rows; Y, R: 8-byte rows;
+ * Yq: 4-byte rows; bias: 16 bytes; part: 8 bytes).
+ * sdp_gemm_mx_applies: 1 iff M >= 1, K % 128 == 0, N % 32 == 0 (a pure function).
+ * Replaces, with the switch on, the PW_up / PW_down 1x1 convs of ConvMixer (layers.py:79-91)
+ * and ff_linear1 / ff_linear2 (layers.py:306-309) with the LayerNorm in front of them.
+ */
+int sdp_mx_quant_rows(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_gstride, int x_off,
+                      const float* stats, void* Q, int64_t ldq, void* S, int64_t lds, int M, int K,
+                      void* stream);
+int sdp_gemm_mx(const void* Xq, int64_t ldxq, const void* Xs, int64_t ldxs, const void* Wq, int64_t ldwq,
+                const void* Ws, int64_t ldws, const float* bias, const void* R, int64_t ldr, int r_grp,
+                int64_t r_gstride, int r_off, void* Y, int64_t ldy, int y_grp, int64_t y_gstride, int y_off,
+                void* Yq, int64_t ldyq, void* Ys, int64_t ldys, int M, int N, int K, int act, int resid_pre,
+                float* part, void* stream);
+int sdp_gemm_mx_applies(int M, int N, int K, int out_is_mx);
 /* Test hook: force the generic kernel (returns the previous setting). */
 int sdp_gemm_force_generic(int on);
 /* Select the bf16 fast kernel: 14 = 8-phase ping-pong 256x256x64 with the

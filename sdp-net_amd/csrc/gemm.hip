@@ -1733,7 +1733,7 @@ extern "C" int sdp_gemm_set_group_m(int gm) {
   return old;
 }
 
-static int g_exact_gelu = 0;
+int g_exact_gelu = 0;  // also read by mx.hip
 extern "C" int sdp_gemm_set_exact_gelu(int on) {
   int old = g_exact_gelu;
   g_exact_gelu = on ? 1 : 0;

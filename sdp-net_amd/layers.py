@@ -70,6 +70,41 @@ def _fold(w: torch.Tensor, ln: nn.Module, bias: Optional[torch.Tensor], dt):
     return sp.fold_ln_weight(f32(w), f32(g), f32(b), f32(bias), dt)
 
 
+def _mx_on(dt, M: int, C: int, F_: int, dev) -> bool:
+    """The MLP pair C -> F_ -> C of a bf16 inference forward runs on the MXFP8 path: the switch is on
+    (sdpnet_hip.mx_fp8, set by MainModel's forward), the LN fold is (the pair's bias is the folded
+    one), and sdpnet_hip.mx_pair_applies takes the shapes."""
+    if not (sp.mx_fp8_enabled() and dt == torch.bfloat16 and _LN_FOLD):
+        return False
+    ll = sp.low_latency_enabled()
+    return sp.mx_pair_applies(M, C, F_, ll, sp._cus(dev) if ll else 256)
+
+
+def _mx_weights(module: nn.Module, up_w, up_b, ln: nn.Module, dn_w, dn_b):
+    """MX copies of an MLP pair's weights, quantised from the fp32 LN-folded up weight W * gamma
+    (not from its bf16 copy) and the fp32 down weight; held like the bf16 copies, so a fused
+    AdamW.step(), load_state_dict and invalidate() refresh them."""
+    g = ln.gamma if hasattr(ln, "gamma") else ln.weight
+    b = ln.beta if hasattr(ln, "beta") else ln.bias
+
+    def build():
+        F_, C = dn_w.shape[1], dn_w.shape[0]
+        wf, _, c = _fold(up_w.reshape(F_, C), ln, up_b, torch.float32)
+        return dict(up=sp.mx_quant_rows(_dense(wf), F_, C), up_c=c,
+                    dn=sp.mx_quant_rows(_dense(f32(dn_w.reshape(C, F_))), C, F_), dn_b=f32(dn_b))
+    return cached(module, "mx", [up_w, up_b, dn_w, dn_b, g, b], torch.uint8, build)
+
+
+def _mlp_mx(stream: Rows, M: int, C: int, F_: int, stats: torch.Tensor, w, act: int, part: torch.Tensor):
+    """stream += down(act(up(LN(stream)))) on the block-scaled MFMA: the LayerNorm without affine
+    goes into the quantiser, the hidden activations from the up GEMM to the down GEMM as MX (no
+    bf16 round trip); emits the stream's LN partials."""
+    xq = sp.mx_quant_rows(stream, M, C, stats=stats)
+    hid = sp.mx_empty(M, F_, stream.t.device)
+    sp.gemm_mx(xq, w["up"], M, F_, C, out_mx=hid, bias=w["up_c"], act=act)
+    sp.gemm_mx(hid, w["dn"], M, C, F_, y=stream, bias=w["dn_b"], resid=stream, part=part)
+
+
 class LayerNorm(nn.Module):
     """Channel LayerNorm over dim 1 of NCHW, biased variance, eps 1e-6
     (layers.py:12-24).  On the token layout it is a row LN over C."""
@@ -221,6 +256,11 @@ class ConvMixer(nn.Module):
         sp.dwconv(img, w["dw_w"], w["dw_b"], _dense(dwo), B, H, W, C, w["k"], stats=stats, ln_gamma=g1, ln_beta=b1)
         # x_ = act(PW(DW(LN1 x)) + b) + x      (layers.py:102); emits x_'s LN partials
         sp.gemm(_dense(dwo), w["cc_w"], img, M, C, C, bias=w["cc_b"], resid=img, act=a, part=part)
+        if _mx_on(dt, M, C, 4 * C, dev):
+            up, dn = self.conv1d[0], self.conv1d[2]
+            wm = _mx_weights(self, up.weight, up.bias, self.layer_norm_2, dn.weight, dn.bias)
+            _mlp_mx(img, M, C, 4 * C, _ln_stats(part, img, M, C, self.layer_norm_2.eps), wm, a, part)
+            return
         # hid = act(PW_up(LN2 x_) + b) with LN2 folded into the GEMM (layers.py:103)
         hid = torch.empty(M, 4 * C, dtype=dt, device=dev)
         if _LN_FOLD:
@@ -498,6 +538,12 @@ class EncoderLayer(nn.Module):
         sp.gemm(xa, w["wo"], _dense(tok), T, C, C, resid=_dense(tok), part=part)  # :300-303
         # LN2 (:307) folded into ff_linear1 (:308)
         F_ = w["w1"].shape[0]
+        if _mx_on(dt, T, C, F_, dev):
+            wm = _mx_weights(self, self.ff_linear1.weight, self.ff_linear1.bias, self.norm2,
+                             self.ff_linear2.weight, self.ff_linear2.bias)
+            _mlp_mx(_dense(tok), T, C, F_, _ln_stats(part, _dense(tok), T, C, w["n2e"]), wm,
+                    act_code(self.activation), part)
+            return tok if R else None
         f = torch.empty(T, F_, dtype=dt, device=dev)
         if _LN_FOLD:
             st2 = _ln_stats(part, _dense(tok), T, C, w["n2e"])

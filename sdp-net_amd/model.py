@@ -186,7 +186,7 @@ class MainModel(SdPModel):
                 return torch.ops.sdpnet.main_forward_raw(x, self._sdp_handle, num_registers, code)
             return torch.ops.sdpnet.main_forward(x, self._sdp_handle, num_registers, code)
         if _hooked(self):
-            with sp.low_latency(self._low_latency_on()):
+            with sp.low_latency(self._low_latency_on()), sp.mx_fp8(self._mx_fp8_on()):
                 return self._forward_modules(x, num_registers, return_raw_outputs)
         if self._fp32_stream_eval(x):
             import sdpnet_train
@@ -216,9 +216,21 @@ class MainModel(SdPModel):
             on = sp.low_latency_enabled() if env is None else env != "0"
         return bool(on)
 
+    def _mx_fp8_on(self) -> bool:
+        """The eligible MLP pairs of a bf16 eval forward on the block-scaled FP8 GEMM
+        (sdpnet_hip.mx_fp8): model.mx_fp8 = True / False, or None (the default) for SDPNET_MX_FP8
+        (unset: whatever an enclosing ``with sdpnet_hip.mx_fp8():`` says, i.e. off by default).
+        Precedence and scoping as _low_latency_on.  fp32 forwards, eval_fp32_stream and every
+        training entry point never look at it."""
+        on = getattr(self, "mx_fp8", None)
+        if on is None:
+            env = os.environ.get("SDPNET_MX_FP8")
+            on = sp.mx_fp8_enabled() if env is None else env != "0"
+        return bool(on)
+
     def _fused_forward(self, x: torch.Tensor, num_registers: int, dt, return_raw_outputs: bool):
         # (also the body of the torch.compile custom ops, sdpnet_ops.main_forward[_raw])
-        with torch.no_grad(), sp.low_latency(self._low_latency_on()):
+        with torch.no_grad(), sp.low_latency(self._low_latency_on()), sp.mx_fp8(self._mx_fp8_on()):
             B, _, Hp, Wp, _, C = geometry(self, x.shape, num_registers)
             ncls = out_features(self)
             self._prepare(dt, Hp, Wp)

@@ -184,8 +184,8 @@ class GraphedForward:
     A replay never computes with stale prepared weights: every call compares the version key
     ``cached`` uses (version counter and address of every parameter) and the count of
     ``invalidate`` / ``load_state_dict`` calls with those of the capture, and captures again when
-    either changed, or when the model's low_latency setting did.  Whatever ``model(x)`` would run
-    eagerly is what is captured (streams, low_latency, final_rows ...); no environment variable
+    either changed, or when the model's low_latency or mx_fp8 setting did.  Whatever ``model(x)`` would run
+    eagerly is what is captured (streams, low_latency, mx_fp8, final_rows ...); no environment variable
     and no queue setting is touched."""
 
     def __init__(self, model: nn.Module, example: torch.Tensor, num_registers: int = 3):
@@ -204,8 +204,10 @@ class GraphedForward:
 
     def _current_state(self):
         ll = getattr(self.model, "_low_latency_on", None)
+        mx = getattr(self.model, "_mx_fp8_on", None)
         return (_key(list(self.model.parameters()), self._x.dtype, self._x.device), _INVALIDATIONS,
-                ll() if ll is not None else sp.low_latency_enabled())
+                ll() if ll is not None else sp.low_latency_enabled(),
+                mx() if mx is not None else sp.mx_fp8_enabled())
 
     def _capture(self):
         dev = self._x.device

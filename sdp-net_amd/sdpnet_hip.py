@@ -40,6 +40,10 @@ _SIGS = {
     "sdp_gemm_splitk": ([_i32, _vp, _i64, *_ROWMAP, _vp, _i64, _vp, _vp, _i64, *_ROWMAP, _vp, _i64, *_ROWMAP,
                          _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp], _i32),
     "sdp_gemm_splitk_ws_bytes": ([_i32, _i32, _i32, _i32], _i64),
+    "sdp_mx_quant_rows": ([_i32, _vp, _i64, *_ROWMAP, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp], _i32),
+    "sdp_gemm_mx": ([_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, *_ROWMAP, _vp, _i64, *_ROWMAP,
+                     _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
+    "sdp_gemm_mx_applies": ([_i32, _i32, _i32, _i32], _i32),
     "sdp_gemm_force_generic": ([_i32], _i32),
     "sdp_gemm_set_fast_kernel": ([_i32], _i32),
     "sdp_gemm_set_store_policy": ([_i32], _i32),
@@ -469,6 +473,130 @@ def gemm_splitk(x: Rows, w: torch.Tensor, y: Rows, M: int, N: int, K: int, bm: i
                                _ptr(part), bm, splits, _ptr(ws), ws.numel() * 4 if ws is not None else 0,
                                _stream(y.t))
     _check(rc, "gemm_splitk")
+
+
+# ---------------------------------------------------------------------------
+# MXFP8 inference: block-scaled e4m3 GEMMs for the MLP pairs (opt-in).
+_MX_FP8 = False
+
+
+def set_mx_fp8(on: bool) -> bool:
+    """Let the eligible MLP pairs of a bf16 inference forward (layers.py) run on ``gemm_mx``;
+    returns the previous value.  Off by default.  ``gemm()`` itself never looks at it."""
+    global _MX_FP8
+    old, _MX_FP8 = _MX_FP8, bool(on)
+    return old
+
+
+def mx_fp8_enabled() -> bool:
+    return _MX_FP8
+
+
+class mx_fp8:
+    """``with mx_fp8(on=True):`` -- set_mx_fp8 for the block, restored on exit."""
+
+    def __init__(self, on: bool = True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.old = set_mx_fp8(self.on)
+        return self
+
+    def __exit__(self, *exc):
+        set_mx_fp8(self.old)
+        return False
+
+
+@dataclass
+class MX:
+    """An MX operand (include/sdpnet_hip.h, "MX operand format"): q uint8 [rows, K] e4m3fn bytes,
+    s uint8 [rows, K / 32] E8M0 scale codes, both dense rows of contiguous tensors."""
+    q: torch.Tensor
+    s: torch.Tensor
+
+    def args(self):
+        return [self.q.data_ptr(), self.q.stride(0), self.s.data_ptr(), self.s.stride(0)]
+
+
+def mx_empty(rows: int, K: int, device) -> MX:
+    return MX(torch.empty(rows, K, dtype=torch.uint8, device=device),
+              torch.empty(rows, K // 32, dtype=torch.uint8, device=device))
+
+
+def mx_applies(M: int, N: int, K: int, out_is_mx: bool = False) -> bool:
+    """Whether ``gemm_mx`` takes the shape: M >= 1, K a multiple of 128, N a multiple of 32 (both
+    output kinds work in whole 32-column blocks).  A pure function (no library call), equal to
+    sdp_gemm_mx_applies."""
+    return M >= 1 and N >= 32 and N % 32 == 0 and K >= 128 and K % 128 == 0
+
+
+def mx_pair_applies(M: int, C: int, F: int, low_latency: bool = False, cus: int = 256) -> bool:
+    """Whether an MLP pair (C -> F with MX output, F -> C with residual and LN partials) runs on
+    ``gemm_mx`` when the switch is on: both GEMMs are eligible, the C-wide output has whole
+    64-column chunks, and -- with ``low_latency`` on -- ``gemm_split_plan`` takes neither GEMM
+    (such a pair stays on split-K).  A pure function."""
+    if not (mx_applies(M, F, C, True) and mx_applies(M, C, F, False) and C % 64 == 0):
+        return False
+    if low_latency and (gemm_split_plan(M, F, C, cus) is not None or gemm_split_plan(M, C, F, cus) is not None):
+        return False
+    return True
+
+
+def _mx_ok(o: MX, rows: int, K: int) -> bool:
+    return (o.q.dtype == o.s.dtype == torch.uint8 and o.q.dim() == o.s.dim() == 2 and o.q.stride(1) == 1
+            and o.s.stride(1) == 1 and o.q.shape[0] >= rows and o.s.shape[0] >= rows and o.q.shape[1] >= K
+            and o.s.shape[1] >= K // 32)
+
+
+def mx_quant_rows(x: Rows, M: int, K: int, stats: Optional[torch.Tensor] = None, out: Optional[MX] = None) -> MX:
+    """Quantise the M logical rows of x (bf16 or fp32) to MX.  stats [M, 2] (mean, rstd): the
+    LayerNorm without affine, (x - mean) * rstd in fp32, is applied first."""
+    _need_cuda(x.t, stats)
+    dt = dcode(x.t.dtype)
+    _req(M >= 0 and K > 0 and K % 128 == 0 and x.ld >= K, "shape")
+    if out is None:
+        out = mx_empty(M, K, x.t.device)
+    _need_cuda(out.q, out.s)
+    _req(_mx_ok(out, M, K), "MX output")
+    _req(M == 0 or _fits(x.t, _max_row(x, M) * x.ld + K), "storage bounds")
+    _req(stats is None or (stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() >= 2 * M))
+    rc = lib().sdp_mx_quant_rows(dt, *x.args(), _ptr(stats), *out.args(), M, K, _stream(out.q))
+    _check(rc, "mx_quant_rows")
+    return out
+
+
+def gemm_mx(x: MX, w: MX, M: int, N: int, K: int, y: Optional[Rows] = None, out_mx: Optional[MX] = None,
+            bias: Optional[torch.Tensor] = None, resid: Optional[Rows] = None, act: int = 0,
+            resid_pre: bool = False, part: Optional[torch.Tensor] = None):
+    """epilogue(x . w^T) of MX operands on the block-scaled MFMA (epilogue as ``gemm`` without the
+    LN fold).  Exactly one of y (bf16 rows) and out_mx (MX of the fp32 epilogue values, blocks along
+    N; no resid, no part)."""
+    _need_cuda(x.q, x.s, w.q, w.s, bias)
+    _req((y is None) != (out_mx is None), "exactly one output")
+    _req(M >= 0 and mx_applies(max(M, 1), N, K, out_mx is not None), "shape")
+    _req(_mx_ok(x, M, K) and _mx_ok(w, N, K), "MX operands")
+    _req(bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() >= N))
+    r = [None, 0, 0, 0, 0]
+    if y is not None:
+        _need_cuda(y.t)
+        _req(y.t.dtype == torch.bfloat16 and y.ld >= N)
+        _req(M == 0 or _fits(y.t, _max_row(y, M) * y.ld + N), "storage bounds")
+        if resid is not None:
+            _req(resid.t.dtype == torch.bfloat16 and resid.ld >= N)
+            _req(M == 0 or _fits(resid.t, _max_row(resid, M) * resid.ld + N), "storage bounds")
+            r = [resid.t.data_ptr(), resid.ld, *resid.map()]
+        if part is not None:
+            _req(part.dtype == torch.float32 and part.is_contiguous() and N % 64 == 0)
+            _req(M == 0 or part.numel() >= (_max_row(y, M) + 1) * (N // 64) * 2, "storage bounds")
+        ya, qa, dev = y.args(), [None, 0, None, 0], y.t
+    else:
+        _need_cuda(out_mx.q, out_mx.s)
+        _req(resid is None and part is None, "MX output takes no resid / part")
+        _req(_mx_ok(out_mx, M, N), "MX output")
+        ya, qa, dev = [None, 0, 0, 0, 0], out_mx.args(), out_mx.q
+    rc = lib().sdp_gemm_mx(*x.args(), *w.args(), _ptr(bias), *r, *ya, *qa, M, N, K, act, int(bool(resid_pre)),
+                           _ptr(part), _stream(dev))
+    _check(rc, "gemm_mx")
 
 
 def layernorm(x: Rows, gamma: torch.Tensor, beta: torch.Tensor, eps: float, y: Rows, M: int, C: int):
