@@ -77,6 +77,16 @@
 extern "C" {
 #endif
 
+/*
+ * Operand alignment.  For the entry points listed in DESIGN.md ("Alignment tiers": the inference
+ * GEMMs, LayerNorm and its statistics, the depthwise conv, sdp_attention, the copy / cast /
+ * activation / patchify kernels, the multi-tensor optimizer kernels) every pointer needs the
+ * alignment of its own element type and nothing more, unless the entry point says below that it
+ * returns an error for an operand off some boundary (it then returns before any launch: no output
+ * byte is written).  Wider alignment (16-byte bases and row strides, 8-byte statistics) only selects
+ * a faster kernel; tests/test_gpu_alignment.py holds this.  The training entry points state their
+ * requirements one by one.
+ */
 /* Version string of the library build. */
 const char* sdp_version(void);
 

@@ -1898,7 +1898,10 @@ static int attention_impl(int dtype, const void* QKV, int64_t ldq, void* O, int6
   if (B == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   const float scale = 1.0f / sqrtf((float)head_dim);
-  const bool al = (ldq % 8 == 0) && (ldo % 4 == 0) && ((uintptr_t)QKV % 16 == 0) && ((uintptr_t)O % 8 == 0);
+  // the flash kernels read the q / k norm parameters as f32x4 (frag_norm)
+  auto a16 = [](const float* p) { return (uintptr_t)p % 16 == 0; };
+  const bool al = (ldq % 8 == 0) && (ldo % 4 == 0) && ((uintptr_t)QKV % 16 == 0) && ((uintptr_t)O % 8 == 0) &&
+                  (!norm || (a16(q_gamma) && a16(q_beta) && a16(k_gamma) && a16(k_beta)));
   const int variant = al ? sdp_attention_variant(dtype, N, n_head, head_dim, mask != nullptr) : 0;
   // AttnKV (variants 3, 4, 6) keeps the K / V byte offsets within one image in 32 bits: the padded
   // image's QKV rows must span less than 2^32 bytes

@@ -80,7 +80,8 @@ SDP_DEV void epi_store4(const Epi<T>& e, int64_t m, int n, int N, f32x4 acc) {
   float v[4] = {acc[0], acc[1], acc[2], acc[3]};
   const bool full = (n + 3 < N);
   if (e.lnst) {
-    const float2 st = *(const float2*)(e.lnst + 2 * m);
+    // two floats, not one float2: this is the path a 4-B aligned lnst falls to
+    const float2 st = float2{e.lnst[2 * m], e.lnst[2 * m + 1]};
     const float rmu = st.y * st.x;
 #pragma unroll
     for (int r = 0; r < 4; ++r)
@@ -1955,7 +1956,8 @@ static int gemm_impl(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x
     }
     const bool aligned = (ldy % 4 == 0) && ((uintptr_t)Y % 8 == 0) && (!R || ((ldr % 4 == 0) && ((uintptr_t)R % 8 == 0))) &&
                          (!bias || ((uintptr_t)bias % 16 == 0)) && (ldx % 8 == 0) && ((uintptr_t)X % 16 == 0) &&
-                         (ldw % 8 == 0) && ((uintptr_t)W % 16 == 0);
+                         (ldw % 8 == 0) && ((uintptr_t)W % 16 == 0) &&
+                         (!ln_stats || ((uintptr_t)ln_stats % 8 == 0));  // the fast epilogues read (mean, rstd) as float2
     if (!g_force_generic && aligned && sdp_gemm_variant(dtype, M, N, K) == 1) {
       const int tm = (M + fast::BM - 1) / fast::BM, tn = (N + fast::BN - 1) / fast::BN;
       e.tline = g_tl_buf ? tl_take() : nullptr;
@@ -1964,7 +1966,9 @@ static int gemm_impl(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x
       const bool rows_ok = (N % 8 == 0) && (ldy % 8 == 0) && ((uintptr_t)Y % 16 == 0) &&
                            (!R || ((ldr % 8 == 0) && ((uintptr_t)R % 16 == 0))) && !(R && resid_pre && act != ACT_NONE);
       const int fk = rows_ok ? g_fast_kernel : 9;
-      if (fk == 14 && part && N % 64 == 0) {  // the whole-line epilogue emits the row partial statistics
+      // the whole-line epilogue emits the row partial statistics (float2 stores: an 8-B aligned
+      // buffer; otherwise sdp_gemm_ln computes them from the stored rows)
+      if (fk == 14 && part && N % 64 == 0 && (uintptr_t)part % 8 == 0) {
         e.part = part;
         if (part_done) *part_done = true;
       }

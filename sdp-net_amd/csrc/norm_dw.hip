@@ -126,7 +126,8 @@ static int launch_ln(const void* X, int64_t ldx, RowMap xm, const float* g, cons
                      int64_t ldy, RowMap ym, int M, int C, hipStream_t s) {
   dim3 grid((M + 3) / 4), blk(256);
   const bool vec_ok = (C % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) &&
-                      ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0);
+                      ((uintptr_t)X % 16 == 0) && ((uintptr_t)Y % 16 == 0) &&
+                      ((uintptr_t)g % 16 == 0) && ((uintptr_t)b % 16 == 0);  // gamma / beta are read as f32x4
   const int nv = C / 4;
   if (vec_ok && nv <= 64)
     hipLaunchKernelGGL((layernorm_rows<T, 1>), grid, blk, 0, s, (const T*)X, ldx, xm, g, b, eps, (T*)Y, ldy, ym, M, C);
@@ -221,7 +222,7 @@ extern "C" int sdp_qk_headnorm(int dtype, void* QKV, int64_t ld, int64_t rows, i
 // Row statistics (mean, rstd) for a LayerNorm applied by the consumer kernel.
 // stats[2m] = mean, stats[2m+1] = 1/sqrt(var + eps) of logical row m.
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool VEC>  // VEC: rows are read as 4-element vectors (X % 16, ldx % 4 elements)
 __global__ __launch_bounds__(256) void rowstats_k(const T* __restrict__ X, int64_t ldx, RowMap xm, float eps,
                                                   float* __restrict__ stats, int M, int C) {
   const int lane = threadIdx.x & 63;
@@ -236,7 +237,10 @@ __global__ __launch_bounds__(256) void rowstats_k(const T* __restrict__ X, int64
   for (int i = 0; i < VPL; ++i) {
     const int c4 = lane + i * 64;
     if (c4 < nv) {
-      if constexpr (sizeof(T) == 2) {
+      if constexpr (!VEC) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[i][r] = to_f<T>(xp[c4 * 4 + r]);
+      } else if constexpr (sizeof(T) == 2) {
         bf16x4 t = *(const bf16x4*)(xp + c4 * 4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[i][r] = bf2f((bf16_t)t[r]);
@@ -273,14 +277,17 @@ __global__ __launch_bounds__(256) void rowstats_k(const T* __restrict__ X, int64
 
 extern "C" int sdp_rowstats(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_gstride, int x_off, float eps,
                             float* stats, int M, int C, void* stream) {
-  if (!X || !stats || M < 0 || C <= 0 || C % 4 || C > 2048 || ldx % 4) return (int)hipErrorInvalidValue;
+  if (!X || !stats || M < 0 || C <= 0 || C % 4 || C > 2048) return (int)hipErrorInvalidValue;
+  if (dtype != 0 && dtype != 1) return (int)hipErrorInvalidValue;
   if (M == 0) return 0;
   const RowMap xm = mk_rmap(x_grp, x_gstride, x_off);
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((M + 3) / 4), blk(256);
-  if (dtype == 1) hipLaunchKernelGGL(rowstats_k<bf16_t>, grid, blk, 0, s, (const bf16_t*)X, ldx, xm, eps, stats, M, C);
-  else if (dtype == 0) hipLaunchKernelGGL(rowstats_k<float>, grid, blk, 0, s, (const float*)X, ldx, xm, eps, stats, M, C);
-  else return (int)hipErrorInvalidValue;
+  const bool vec = (ldx % 4 == 0) && ((uintptr_t)X % 16 == 0);  // else the same kernel on element loads
+#define SDP_RS(T, V) hipLaunchKernelGGL((rowstats_k<T, V>), grid, blk, 0, s, (const T*)X, ldx, xm, eps, stats, M, C)
+  if (dtype == 1) { if (vec) SDP_RS(bf16_t, true); else SDP_RS(bf16_t, false); }
+  else { if (vec) SDP_RS(float, true); else SDP_RS(float, false); }
+#undef SDP_RS
   return SDP_CHECK_LAUNCH();
 }
 
@@ -324,7 +331,10 @@ __global__ __launch_bounds__(256) void row_partials_k(const T* __restrict__ X, i
   m2 += __shfl_xor(m2, 1, 64);
   m2 += __shfl_xor(m2, 2, 64);
   m2 += __shfl_xor(m2, 4, 64);
-  if (ok && sub == 0) *(float2*)(part + (pr * nch + c) * 2) = float2{mean, m2};
+  if (ok && sub == 0) {  // two floats: part may be any 4-B aligned buffer
+    part[(pr * nch + c) * 2] = mean;
+    part[(pr * nch + c) * 2 + 1] = m2;
+  }
 }
 
 extern "C" int sdp_row_partials(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_gstride, int x_off, int M,
@@ -350,7 +360,7 @@ __global__ __launch_bounds__(256) void ln_stats_k(const float* __restrict__ part
   const float* p = part + xm(m) * nch * 2;
   float na = 0.f, mean = 0.f, m2 = 0.f;
   for (int c = 0; c < nch; ++c) {
-    const float2 q = *(const float2*)(p + 2 * c);
+    const float2 q = float2{p[2 * c], p[2 * c + 1]};  // part / stats: any 4-B aligned buffer
     const float nb = (float)min(64, C - c * 64);
     const float n = na + nb;
     const float d = q.x - mean;
@@ -358,7 +368,8 @@ __global__ __launch_bounds__(256) void ln_stats_k(const float* __restrict__ part
     m2 += q.y + d * d * (na * nb / n);
     na = n;
   }
-  *(float2*)(stats + 2 * m) = float2{mean, rsqrtf(m2 / (float)C + eps)};
+  stats[2 * m] = mean;
+  stats[2 * m + 1] = rsqrtf(m2 / (float)C + eps);
 }
 
 extern "C" int sdp_ln_stats(const float* part, int x_grp, int64_t x_gstride, int x_off, int M, int C, float eps,
@@ -395,7 +406,10 @@ template <typename T, int KS, int STRIP>
 __global__ __launch_bounds__(DW_THREADS) void dwconv_ln_nhwc(
     const T* __restrict__ X, int64_t ldx, RowMap xm, const float* __restrict__ stats, const float* __restrict__ lg,
     const float* __restrict__ lb, const float* __restrict__ Wt, const float* __restrict__ bias, T* __restrict__ Y,
-    int64_t ldy, RowMap ym, int H, int W, int C, int band, int pitch, int vec_in) {
+    int64_t ldy, RowMap ym, int H, int W, int C, int band, int pitch, int vec) {
+  // vec: bit 0 = 16-B loads of X rows, bit 1 = 4-element stores of Y rows, bit 2 = f32x4 bias loads
+  // (each where base and row stride are aligned for it; element accesses otherwise)
+  const bool vec_in = vec & 1, vec_out = vec & 2, vec_bias = vec & 4;
   constexpr int PAD = KS / 2;
   extern __shared__ __attribute__((aligned(16))) char dsm[];
   T* tile = (T*)dsm;  // [TH][pitch][32]; columns >= W + KS - 1 are zero
@@ -454,7 +468,10 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_ln_nhwc(
 #pragma unroll
           for (int e = 0; e < EPL; ++e) rv[e] = (c + e < C) ? src[e] : from_f<T>(0.f);
         }
-        if (stats) st[u] = *(const float2*)(stats + 2 * (img0 + local[u]));
+        if (stats) {  // two floats: this kernel takes any 4-B aligned stats buffer
+          const float* sp = stats + 2 * (img0 + local[u]);
+          st[u] = float2{sp[0], sp[1]};
+        }
       }
     }
 #pragma unroll
@@ -485,7 +502,11 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_ln_nhwc(
   const int cq = tid & 7;    // channels 4cq .. 4cq+3 of the block
   const int grp = tid >> 3;  // 16 strip workers
   const int cg = c0 + cq * 4;
-  const f32x4 bv = (bias && cg + 3 < C) ? *(const f32x4*)(bias + cg) : f32x4{0.f, 0.f, 0.f, 0.f};
+  f32x4 bv = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (bias && cg + 3 < C) {
+    if (vec_bias) bv = *(const f32x4*)(bias + cg);
+    else bv = f32x4{bias[cg], bias[cg + 1], bias[cg + 2], bias[cg + 3]};
+  }
   const int nstrip = (W + STRIP - 1) / STRIP;
   for (int job = grp; job < hb * nstrip; job += DW_THREADS / 8) {
     const int oh = job / nstrip;
@@ -518,7 +539,7 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_ln_nhwc(
       const int w = w0 + o;
       if (w < W) {
         T* dst = Y + (yrow0 + (int64_t)gh * W + w) * ldy + cg;
-        if (cg + 3 < C) {
+        if (vec_out && cg + 3 < C) {
           if constexpr (sizeof(T) == 2) {
             bf16x4 t;
 #pragma unroll
@@ -552,14 +573,17 @@ static int launch_dw(const void* X, int64_t ldx, RowMap xm, const float* stats, 
   const int nb = (H + band - 1) / band;
   const size_t lds = ((size_t)(band + KS - 1) * row_bytes + 15) / 16 * 16 + (size_t)KS * KS * DW_CB * 4;
   dim3 grid((C + DW_CB - 1) / DW_CB, nb, B);
-  const int vec_in = ((ldx * (int64_t)sizeof(T)) % 16 == 0) && ((uintptr_t)X % 16 == 0);
+  const int64_t es = (int64_t)sizeof(T);
+  const int vec = ((((ldx * es) % 16 == 0) && ((uintptr_t)X % 16 == 0)) ? 1 : 0) |
+                  ((((ldy * es) % (4 * es) == 0) && ((uintptr_t)Y % (4 * es) == 0)) ? 2 : 0) |
+                  (((uintptr_t)bias % 16 == 0) ? 4 : 0);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)dwconv_ln_nhwc<T, KS, STRIP>,
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
   }
   hipLaunchKernelGGL((dwconv_ln_nhwc<T, KS, STRIP>), grid, dim3(DW_THREADS), lds, s, (const T*)X, ldx, xm, stats, lg,
-                     lb, Wt, bias, (T*)Y, ldy, ym, H, W, C, band, pitch, vec_in);
+                     lb, Wt, bias, (T*)Y, ldy, ym, H, W, C, band, pitch, vec);
   return SDP_CHECK_LAUNCH();
 }
 
@@ -1031,13 +1055,13 @@ extern "C" int sdp_dwconv(int dtype, const void* X, int64_t ldx, int x_grp, int6
   if (!X || !Y || !weight || B < 0 || H <= 0 || W <= 0 || C <= 0) return (int)hipErrorInvalidValue;
   if (stats && (!ln_gamma || !ln_beta)) return (int)hipErrorInvalidValue;
   const int esz = dtype == 1 ? 2 : 4;
-  if ((ldy * esz) % 8 || ((uintptr_t)Y % 8) || ((uintptr_t)X % esz)) return (int)hipErrorInvalidValue;
-  if (bias && ((uintptr_t)bias % 16)) return (int)hipErrorInvalidValue;
+  if (((uintptr_t)Y % esz) || ((uintptr_t)X % esz)) return (int)hipErrorInvalidValue;
   if (B == 0) return 0;
   // row maps must be dense or group whole images (see dwconv_ln_nhwc)
   if ((x_grp > 0 && x_grp % (H * W)) || (y_grp > 0 && y_grp % (H * W))) return (int)hipErrorInvalidValue;
   const RowMap xm = mk_rmap(x_grp, x_gstride, x_off), ym = mk_rmap(y_grp, y_gstride, y_off);
   hipStream_t s = (hipStream_t)stream;
+  // the tiers above dwconv_ln_nhwc: 16-B row loads and stores, (mean, rstd) as float2
   const bool v16 = ((ldx * esz) % 16 == 0) && ((uintptr_t)X % 16 == 0) && ((ldy * esz) % 16 == 0) &&
                    ((uintptr_t)Y % 16 == 0) && (!stats || ((uintptr_t)stats % 8 == 0));
   if (g_dw_kernel >= 3 && dtype == 1 && C % 32 == 0 && H <= 16 && W <= 16 && v16 && (k == 3 || k == 5 || k == 7) &&
@@ -1045,7 +1069,8 @@ extern "C" int sdp_dwconv(int dtype, const void* X, int64_t ldx, int x_grp, int6
     const int rc = launch_dw3(k, X, ldx, xm, stats, ln_gamma, ln_beta, weight, bias, Y, ldy, ym, B, H, W, C, s);
     if (rc != -1) return rc;
   }
-  if (g_dw_kernel >= 2 && C % 8 == 0 && v16 && (k == 3 || k == 5 || k == 7)) {
+  // dwconv2_nhwc reads the bias as f32x4
+  if (g_dw_kernel >= 2 && C % 8 == 0 && v16 && ((uintptr_t)bias % 16 == 0) && (k == 3 || k == 5 || k == 7)) {
     const int rc = dtype == 1 ? dw2_dispatch<bf16_t>(k, X, ldx, xm, stats, ln_gamma, ln_beta, weight, bias, Y, ldy, ym, B, H, W, C, s)
                               : dw2_dispatch<float>(k, X, ldx, xm, stats, ln_gamma, ln_beta, weight, bias, Y, ldy, ym, B, H, W, C, s);
     if (rc != -1) return rc;  // -1: image too wide for the dw2 LDS band -> original kernel

@@ -273,7 +273,8 @@ extern "C" int sdp_gemm_wgrad(const void* A, int64_t lda, const void* B, int64_t
   if (ktok % wg::BK && (!zrow || (uintptr_t)zrow % 16)) return (int)hipErrorInvalidValue;
   const int nkt = (ktok + wg::BK - 1) / wg::BK;
   const int splits = (nkt + kchunk_tiles - 1) / kchunk_tiles;
-  if (splits > 1 && split_stride < (int64_t)ni * ldc) return (int)hipErrorInvalidValue;
+  // the slabs C + s * split_stride are stored as f32x4: every slab base 16-B aligned
+  if (splits > 1 && (split_stride < (int64_t)ni * ldc || split_stride % 4)) return (int)hipErrorInvalidValue;
   const int ti = ni / wg::BM, tj = nj / wg::BN;
   const int64_t nwg = (int64_t)ti * tj * splits;
   if (nwg > (1 << 30)) return (int)hipErrorInvalidValue;
@@ -316,7 +317,9 @@ __global__ __launch_bounds__(256) void mt_cast_transpose_k(const MtCastT* __rest
   const MtCastT e = ent[t.x];
   const int r0 = t.y, c0 = t.z, tid = threadIdx.x;
   const int cc = (tid & 15) * 4;
-  const bool vec = (e.C & 3) == 0;
+  // float4 loads of the source rows: C % 4 and a 16-B aligned base (a master weight may be a view
+  // of a flat buffer at any 4-B offset)
+  const bool vec = (e.C & 3) == 0 && ((uintptr_t)e.src & 15) == 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const int rr = (tid >> 4) + 16 * i;

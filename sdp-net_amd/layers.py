@@ -87,11 +87,16 @@ def _mx_weights(module: nn.Module, up_w, up_b, ln: nn.Module, dn_w, dn_b):
     g = ln.gamma if hasattr(ln, "gamma") else ln.weight
     b = ln.beta if hasattr(ln, "beta") else ln.bias
 
+    def al16(t):
+        # sdp_mx_quant_rows / sdp_gemm_mx refuse an operand off a 16-B boundary (sdpnet_hip.h): a
+        # parameter that is a view into a flat buffer is copied once, into this cache
+        return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
     def build():
         F_, C = dn_w.shape[1], dn_w.shape[0]
         wf, _, c = _fold(up_w.reshape(F_, C), ln, up_b, torch.float32)
         return dict(up=sp.mx_quant_rows(_dense(wf), F_, C), up_c=c,
-                    dn=sp.mx_quant_rows(_dense(f32(dn_w.reshape(C, F_))), C, F_), dn_b=f32(dn_b))
+                    dn=sp.mx_quant_rows(_dense(al16(f32(dn_w.reshape(C, F_)))), C, F_), dn_b=al16(f32(dn_b)))
     return cached(module, "mx", [up_w, up_b, dn_w, dn_b, g, b], torch.uint8, build)
 
 

@@ -445,14 +445,23 @@ _ADD_LN = os.environ.get("SDPNET_TRAIN_ADD_LN", "1") != "0"
 _LN_EMIT = os.environ.get("SDPNET_TRAIN_LN_EMIT", "1") != "0"
 
 
+def _ln_fwd_rows(x: Rows, eps: float, g: torch.Tensor, b: torch.Tensor, st: torch.Tensor, y: Rows, M: int, C: int):
+    """LayerNorm rows and their statistics: sdp_ln_fwd where it applies (C % 8 == 0, C <= 2048, rows
+    and parameters 16-B aligned -- it refuses anything else, sdpnet_hip.h; a parameter may be a
+    view of a flat buffer), else the statistics and the LayerNorm as two passes.  The condition is
+    ln_fwd_impl's (train.hip) but for ``st``, which every caller here allocates itself (8-B aligned)."""
+    if C % 8 == 0 and C <= 2048 and x.ld % 8 == 0 and y.ld % 8 == 0 and \
+            all(t.data_ptr() % 16 == 0 for t in (x.t, y.t, g, b)):
+        sp.ln_fwd(x, eps, g, b, st, y, M, C)              # one pass: stats + normalized rows
+    else:
+        sp.rowstats(x, eps, st, M, C)
+        sp.ln_apply(x, st, g, b, y, M, C)
+
+
 def _ln_fwd(x: Rows, M: int, C: int, g: torch.Tensor, b: torch.Tensor, eps: float, dt):
     st = _empty((M, 2), torch.float32, x.t.device)
     a = _empty((M, C), dt, x.t.device)
-    if C % 8 == 0 and C <= 2048 and x.ld % 8 == 0:
-        sp.ln_fwd(x, eps, g, b, st, _dense(a), M, C)      # one pass: stats + normalized rows
-    else:
-        sp.rowstats(x, eps, st, M, C)
-        sp.ln_apply(x, st, g, b, _dense(a), M, C)
+    _ln_fwd_rows(x, eps, g, b, st, _dense(a), M, C)
     return a, st
 
 
@@ -653,14 +662,9 @@ class _EncoderFn(torch.autograd.Function):
             rk = Rows(qkv, hd, Hn, 3 * Hn, Hn)
             sq = _empty((T * Hn, 2), torch.float32, dev)
             sk = _empty((T * Hn, 2), torch.float32, dev)
-            if hd % 8 == 0:  # one pass, several heads per wave (ln_fwd_sm)
-                sp.ln_fwd(rq, e.q_norm.eps, W_["qg"], W_["qb"], sq, Rows(qkvn, hd, Hn, 3 * Hn, 0), T * Hn, hd)
-                sp.ln_fwd(rk, e.k_norm.eps, W_["kg"], W_["kb"], sk, Rows(qkvn, hd, Hn, 3 * Hn, Hn), T * Hn, hd)
-            else:
-                sp.rowstats(rq, e.q_norm.eps, sq, T * Hn, hd)
-                sp.rowstats(rk, e.k_norm.eps, sk, T * Hn, hd)
-                sp.ln_apply(rq, sq, W_["qg"], W_["qb"], Rows(qkvn, hd, Hn, 3 * Hn, 0), T * Hn, hd)
-                sp.ln_apply(rk, sk, W_["kg"], W_["kb"], Rows(qkvn, hd, Hn, 3 * Hn, Hn), T * Hn, hd)
+            # one pass where hd % 8 == 0 (several heads per wave, ln_fwd_sm), else two
+            _ln_fwd_rows(rq, e.q_norm.eps, W_["qg"], W_["qb"], sq, Rows(qkvn, hd, Hn, 3 * Hn, 0), T * Hn, hd)
+            _ln_fwd_rows(rk, e.k_norm.eps, W_["kg"], W_["kb"], sk, Rows(qkvn, hd, Hn, 3 * Hn, Hn), T * Hn, hd)
         # attention (:289-298): S = QK^T, P = softmax(S / sqrt(hd)), Pd = dropout(P), O = Pd V
         Np = (N + 7) // 8 * 8
         Z = B * Hn
