@@ -796,6 +796,63 @@ int sdp_train_batch_aug(const uint8_t* images, int nhwc, const int64_t* labels, 
                         const int32_t* plan, int B, int H, int W, int dtype_out, void* out, float* targets,
                         int64_t ldt, int K, void* stream);
 
+/* RandomResizedCrop + RandomHorizontalFlip of hf_dataset_generator.py:43-57 (train_transforms) on B
+ * decoded uint8 RGB HWC images of any sizes, with the resampler of sdp_val_preprocess (Pillow
+ * 12.2.0's 8-bit bicubic: double taps without FMA contraction, 22-bit fixed point, the horizontal
+ * pass first, a pass skipped when its axis keeps its size):
+ *   out_u8[b] = PIL.Image.fromarray(img_b).crop((left, top, left + w, top + h))
+ *                  .resize((OW, OH), BICUBIC), mirrored left-right when flip is set, bit for bit.
+ * The box is an image of its own: taps are computed from (w, OW) and (h, OH) and clamp at the
+ * box's edges; only the row stride is the full image's W * 3.
+ *   pix, offs[B], hw[B][2]: as for sdp_val_preprocess.
+ *   plan: int32 [B][8] on the device (one host copy): {top, left, h, w, flip, 0, 0, 0} with
+ *   0 <= top, 1 <= h, top + h <= H, 0 <= left, 1 <= w, left + w <= W, which the host validates
+ *   before the upload together with h <= 100 w (Pillow reorders its passes above that).  The
+ *   kernels clamp every word again (into image b, to max_w columns and to the tmp_stride /
+ *   (OW * 4) rows of image b's slice of tmp), so a bad plan word cannot address outside image b,
+ *   tmp or out_u8; its pixels are then unspecified.
+ *   KMAX: the largest tap count over the batch, ceil(2 * max(1, In / Out)) * 2 + 1 over (w, OW)
+ *   and (h, OH) of every box (<= 160).  ws: B * (OW + OH) * (2 + KMAX) int32 of device workspace;
+ *   tmp: B * tmp_stride bytes, tmp_stride >= max box h * OW * 4; max_w: the widest box
+ *   (<= 40960; its RGBX row is staged in LDS).
+ *   out_u8: [B][OH][OW][3].  B == 0 is a no-op. */
+int sdp_resized_crop(const uint8_t* pix, const int64_t* offs, const int* hw, const int32_t* plan, int B,
+                     int OH, int OW, int KMAX, void* ws, uint8_t* tmp, int64_t tmp_stride, int max_w,
+                     uint8_t* out_u8, void* stream);
+
+/* torchvision RandAugment()'s ops on a uint8 batch [B][H][W][3] (hf_dataset_generator.py:43-57,
+ * between the crop / flip and ToImage), num_ops (1..4) ops per image in sequence, each reading
+ * its predecessor's output, bit-exact to the Pillow 12.2.0 calls torchvision makes for PIL images.
+ * The device does integer and fp32 arithmetic only; what Pillow or torchvision compute in double
+ * precision arrives pre-digested in the plan.
+ *   in, out: [B][H][W][3], contiguous; out may equal in (in place), otherwise they must not
+ *   overlap.  scratch: B * H * W * 3 bytes of device workspace, overlapping neither.
+ *   plan: int32 [B][num_ops][8] on the device (one host copy), {op, p1 .. p7}:
+ *     0 Identity
+ *     1 ShearX, 2 ShearY, 3 TranslateX, 4 TranslateY, 5 Rotate: Image.transform(size, AFFINE, m,
+ *       NEAREST), fill 0 (Rotate: Image.rotate's matrix) on Pillow's 16.16 fixed-point path:
+ *       p1..p6 = a0..a5 with FIX(v) = floor(v * 65536 + 0.5), a0, a1, a3, a4 = FIX(m0), FIX(m1),
+ *       FIX(m3), FIX(m4), a2 = FIX(m2 + m0 / 2 + m1 / 2), a5 = FIX(m5 + m3 / 2 + m4 / 2);
+ *       out(y, x) = in(yin, xin), xin = (a2 + a0 x + a1 y) >> 16, yin = (a5 + a3 x + a4 y) >> 16,
+ *       0 when (yin, xin) is outside the image.  The host refuses a matrix that maps a corner
+ *       (0 | W, 0 | H) outside +-32768, where Pillow leaves this path.
+ *     6 Brightness, 7 Color, 8 Contrast, 9 Sharpness: p1 = bits of the fp32 factor f;
+ *       ImageEnhance's blend(degenerate, in, f): per byte t = fl(fl(d) + fl(f * fl(s - d))) (no FMA
+ *       contraction), (uint8)(int)t when 0 <= f <= 1, else t clamped to [0, 255] and truncated.
+ *       d: 0 | L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16 in all channels | the constant
+ *       int(mean(L) + 0.5), the mean an integer sum divided in double | ImageFilter.SMOOTH:
+ *       floor(sum / 13 + 0.5) of (1 1 1; 1 5 1; 1 1 1) inside, the one-pixel border unchanged
+ *       (the host refuses Sharpness on H < 3 or W < 3, where Pillow raises).
+ *     10 Posterize: v & p1.  11 Solarize: v < p1 ? v : 255 - v (p1: the first inverted value).
+ *     12 AutoContrast (ImageOps.autocontrast, cutoff 0), 13 Equalize (ImageOps.equalize), per
+ *       channel from its 256-bin histogram.
+ *   Any other op code acts as Identity.  Plan words are compared, or enter arithmetic whose
+ *   result is range-checked before it addresses a pixel: no plan can reach outside image b.
+ * One workgroup per image; an image of at most 224 * 224 * 3 bytes is kept in LDS across the ops,
+ * a larger one is worked on in out.  H * W * 3 < 2^31.  B == 0 is a no-op. */
+int sdp_randaugment(const uint8_t* in, uint8_t* out, const int32_t* plan, int B, int H, int W, int num_ops,
+                    uint8_t* scratch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,9 @@
 //    horizontal pass first, a pass skipped when its axis keeps its size.  Only the
 //    cropped window is produced (each output pixel depends on its own taps only, so the
 //    crop commutes with the resize bit for bit).
+//  * sdp_resized_crop — the head of the reference's training transform
+//    (hf_dataset_generator.py:43-57): RandomResizedCrop(BICUBIC) + RandomHorizontalFlip with the
+//    same resampler, the crop box taken as an image of its own, into a uint8 HWC batch.
 //  * sdp_logits_metrics — per-row cross-entropy, BCE-with-logits against the smoothed
 //    one-hot target and top-1 hit (model_test.py:69-82, training_utilities.py:95-107).
 #include "common.h"
@@ -40,17 +43,10 @@ SDP_DEV int64_t tap_at(int b, int x, int t, int CW, int CH, int KMAX) {
   return ((int64_t)b * KMAX + x) * (CW + CH) + t;
 }
 
-__global__ void coef_k(const int* __restrict__ hw, int B, int RH, int RW, int top, int left, int CH, int CW, int KMAX,
-                       Tab tab) {
+// One column of the tap table: precompute_coeffs(inSize, 0, inSize, outSize, bicubic) for output
+// position xx, written as entry t of image b.
+__device__ void coef_entry(int inSize, int outSize, int xx, int b, int t, int CW, int CH, int KMAX, Tab tab) {
 #pragma clang fp contract(off)
-  const int b = blockIdx.y;
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= CW + CH) return;
-  const bool horiz = t < CW;
-  const int inSize = horiz ? hw[2 * b + 1] : hw[2 * b];
-  const int outSize = horiz ? RW : RH;
-  const int xx = horiz ? left + t : top + (t - CW);
-  // precompute_coeffs(inSize, 0, inSize, outSize, bicubic)
   double filterscale, scale;
   filterscale = scale = (double)inSize / outSize;
   if (filterscale < 1.0) filterscale = 1.0;
@@ -76,6 +72,16 @@ __global__ void coef_k(const int* __restrict__ hw, int B, int RH, int RW, int to
   int* bd = tab.bounds + ((int64_t)b * (CW + CH) + t) * 2;
   bd[0] = xmin;
   bd[1] = n;
+}
+
+__global__ void coef_k(const int* __restrict__ hw, int B, int RH, int RW, int top, int left, int CH, int CW, int KMAX,
+                       Tab tab) {
+  const int b = blockIdx.y;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= CW + CH) return;
+  const bool horiz = t < CW;
+  coef_entry(horiz ? hw[2 * b + 1] : hw[2 * b], horiz ? RW : RH, horiz ? left + t : top + (t - CW), b, t, CW, CH,
+             KMAX, tab);
 }
 
 SDP_DEV uint8_t clip8(int v) {
@@ -196,6 +202,129 @@ __global__ void vpass_k(const int* __restrict__ hw, int RH, int top, int CH, int
     }
   }
 }
+
+// ---- sdp_resized_crop: RandomResizedCrop + RandomHorizontalFlip with the same resampler ----
+// The box of image b is an image of its own: tables from (w, OW) and (h, OH), taps clamped at the
+// box, source rows addressed with the full image's stride.  Plan words per image (int32):
+// {top, left, h, w, flip, 0, 0, 0}.  The host validates them; the clamps below keep a bad word
+// inside image b, inside a wave's LDS row (max_w) and inside image b's slice of tmp (max_h).
+constexpr int CROP_PER = 8;
+struct Box {
+  int top, left, h, w, flip;
+};
+SDP_DEV Box crop_box(const int* __restrict__ plan, int b, int H, int W, int max_h, int max_w) {
+  const int* q = plan + (int64_t)b * CROP_PER;
+  Box g;
+  g.top = min(max(q[0], 0), H - 1);
+  g.left = min(max(q[1], 0), W - 1);
+  g.h = min(max(q[2], 1), min(H - g.top, max_h));
+  g.w = min(max(q[3], 1), min(W - g.left, max_w));
+  g.flip = q[4] & 1;
+  return g;
+}
+
+__global__ void crop_coef_k(const int* __restrict__ hw, const int* __restrict__ plan, int OH, int OW, int KMAX,
+                            Tab tab, int max_h, int max_w) {
+  const int b = blockIdx.y;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int H = hw[2 * b], W = hw[2 * b + 1];
+  if (t >= OW + OH || H <= 0 || W <= 0) return;
+  const Box g = crop_box(plan, b, H, W, max_h, max_w);
+  const bool horiz = t < OW;
+  coef_entry(horiz ? g.w : g.h, horiz ? OW : OH, horiz ? t : t - OW, b, t, OW, OH, KMAX, tab);
+}
+
+// Horizontal pass over the box rows the vertical pass needs; one wave per row as in hpass_k, the
+// staged row being the box's w pixels.  Output: tmp[b][y][j] RGBX, y relative to the box.
+__global__ __launch_bounds__(256) void crop_hpass_k(const uint8_t* __restrict__ pix, const int64_t* __restrict__ offs,
+                                                    const int* __restrict__ hw, const int* __restrict__ plan, int OH,
+                                                    int OW, int KMAX, Tab tab, uint8_t* __restrict__ tmp,
+                                                    int64_t tmp_stride, int max_h, int max_w) {
+  extern __shared__ uint32_t lds_rows[];  // [waves][max_w] RGBX
+  const int b = blockIdx.y;
+  const int H = hw[2 * b], W = hw[2 * b + 1];
+  if (H <= 0 || W <= 0) return;
+  const Box g = crop_box(plan, b, H, W, max_h, max_w);
+  const bool need_h = g.w != OW, need_v = g.h != OH;
+  int y0, y1;
+  rows_needed(tab, b, OH, OW, need_v, 0, y0, y1);
+  y0 = max(y0, 0);
+  y1 = min(y1, g.h);
+  const uint8_t* img = pix + offs[b];
+  uint32_t* out = (uint32_t*)(tmp + (int64_t)b * tmp_stride);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  uint32_t* srow = lds_rows + (int64_t)wave * max_w;
+  for (int y = y0 + blockIdx.x * nw + wave; y < y1; y += gridDim.x * nw) {
+    const uint8_t* row = img + ((int64_t)(g.top + y) * W + g.left) * 3;
+    __builtin_amdgcn_wave_barrier();  // previous row's tap reads precede the overwrite
+    for (int i = lane; i < g.w * 3; i += 64) ((uint8_t*)srow)[(i / 3) * 4 + (i % 3)] = row[i];
+    __builtin_amdgcn_wave_barrier();
+    for (int j = lane; j < OW; j += 64) {
+      uint32_t o;
+      if (!need_h) {
+        o = srow[j] & 0x00ffffffu;
+      } else {
+        const int* bd = tab.bounds + ((int64_t)b * (OW + OH) + j) * 2;
+        const int* k = tab.coef + tap_at(b, 0, j, OW, OH, KMAX);
+        const int xmin = bd[0], n = bd[1];
+        int s0 = 1 << (PREC - 1), s1 = s0, s2 = s0;
+        for (int x = 0; x < n; ++x) {
+          const int w = k[(int64_t)x * (OW + OH)];
+          const uint32_t px = srow[xmin + x];
+          s0 += (int)(px & 0xff) * w;
+          s1 += (int)((px >> 8) & 0xff) * w;
+          s2 += (int)((px >> 16) & 0xff) * w;
+        }
+        o = (uint32_t)clip8(s0) | ((uint32_t)clip8(s1) << 8) | ((uint32_t)clip8(s2) << 16);
+      }
+      out[(int64_t)y * OW + j] = o;
+    }
+  }
+}
+
+// Vertical pass into the uint8 HWC output, mirrored left-right when the flip bit is set.
+__global__ void crop_vpass_k(const int* __restrict__ hw, const int* __restrict__ plan, int OH, int OW, int KMAX,
+                             Tab tab, const uint8_t* __restrict__ tmp, int64_t tmp_stride, int max_h, int max_w,
+                             uint8_t* __restrict__ out_u8) {
+  const int b = blockIdx.y;
+  const int H = hw[2 * b], W = hw[2 * b + 1];
+  if (H <= 0 || W <= 0) return;
+  const Box g = crop_box(plan, b, H, W, max_h, max_w);
+  const bool need_v = g.h != OH;
+  const uint32_t* src = (const uint32_t*)(tmp + (int64_t)b * tmp_stride);
+  const int64_t total = (int64_t)OH * OW;
+  for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+       idx += (int64_t)gridDim.x * blockDim.x) {
+    const int i = (int)(idx / OW), j = (int)(idx % OW);
+    uint8_t u[3];
+    if (!need_v) {
+      const uint32_t px = src[(int64_t)i * OW + j];
+      u[0] = px & 0xff;
+      u[1] = (px >> 8) & 0xff;
+      u[2] = (px >> 16) & 0xff;
+    } else {
+      const int* bd = tab.bounds + ((int64_t)b * (OW + OH) + OW + i) * 2;
+      const int* k = tab.coef + tap_at(b, 0, OW + i, OW, OH, KMAX);
+      const int ymin = bd[0], n = bd[1];
+      int s0 = 1 << (PREC - 1), s1 = s0, s2 = s0;
+      const uint32_t* p = src + (int64_t)ymin * OW + j;
+      for (int y = 0; y < n; ++y) {
+        const int w = k[(int64_t)y * (OW + OH)];
+        const uint32_t px = p[(int64_t)y * OW];
+        s0 += (int)(px & 0xff) * w;
+        s1 += (int)((px >> 8) & 0xff) * w;
+        s2 += (int)((px >> 16) & 0xff) * w;
+      }
+      u[0] = clip8(s0);
+      u[1] = clip8(s1);
+      u[2] = clip8(s2);
+    }
+    uint8_t* o = out_u8 + (((int64_t)b * OH + i) * OW + (g.flip ? OW - 1 - j : j)) * 3;
+    o[0] = u[0];
+    o[1] = u[1];
+    o[2] = u[2];
+  }
+}
 }  // namespace pre
 
 extern "C" int sdp_val_preprocess(const uint8_t* pix, const int64_t* offs, const int* hw, int B, int RH, int RW,
@@ -237,6 +366,37 @@ extern "C" int sdp_val_preprocess(const uint8_t* pix, const int64_t* offs, const
                        (const uint8_t*)tmp, tmp_stride, nm, (bf16_t*)out, out_u8);
   else
     return (int)hipErrorInvalidValue;
+  return SDP_CHECK_LAUNCH();
+}
+
+extern "C" int sdp_resized_crop(const uint8_t* pix, const int64_t* offs, const int* hw, const int32_t* plan, int B,
+                                int OH, int OW, int KMAX, void* ws, uint8_t* tmp, int64_t tmp_stride, int max_w,
+                                uint8_t* out_u8, void* stream) {
+  if (B < 0 || OH <= 0 || OW <= 0 || KMAX <= 0 || KMAX > 160 || max_w <= 0 || max_w > 40960 ||
+      tmp_stride < (int64_t)OW * 4)
+    return (int)hipErrorInvalidValue;
+  if (B == 0) return 0;
+  if (!pix || !offs || !hw || !plan || !ws || !tmp || !out_u8) return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  pre::Tab tab{(int*)ws, (int*)ws + (int64_t)B * (OW + OH) * 2};
+  const int max_h = (int)std::min<int64_t>(tmp_stride / ((int64_t)OW * 4), 0x7fffffff);
+  hipLaunchKernelGGL(pre::crop_coef_k, dim3((OW + OH + 63) / 64, B), dim3(64), 0, s, hw, plan, OH, OW, KMAX, tab,
+                     max_h, max_w);
+  int nw = 4;
+  while (nw > 1 && (size_t)nw * max_w * 4 > 65536) nw >>= 1;
+  const size_t lds = (size_t)nw * max_w * 4;
+  if (lds > 65536) {
+    static bool raised = false;
+    if (!raised) {
+      (void)hipFuncSetAttribute((const void*)pre::crop_hpass_k, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024);
+      raised = true;
+    }
+  }
+  hipLaunchKernelGGL(pre::crop_hpass_k, dim3(64, B), dim3(64 * nw), lds, s, pix, offs, hw, plan, OH, OW, KMAX, tab,
+                     tmp, tmp_stride, max_h, max_w);
+  hipLaunchKernelGGL(pre::crop_vpass_k, dim3(64, B), dim3(256), 0, s, hw, plan, OH, OW, KMAX, tab,
+                     (const uint8_t*)tmp, tmp_stride, max_h, max_w, out_u8);
   return SDP_CHECK_LAUNCH();
 }
 

@@ -24,9 +24,22 @@ The loader's workers keep decode, RandomResizedCrop and RandAugment (they work o
 and hand over uint8 batches; ``TrainBatchTransform`` draws the random decisions on the host
 (``AugPlan``), uploads pixels, labels and plan in one copy and runs ``sdp_train_batch_aug``
 (csrc/augment.hip), which reproduces the reference's fp32 arithmetic bit for bit.
+
+``TrainImageTransform`` moves the head of ``train_transforms`` onto the device as well:
+
+    RGB -> RandomResizedCrop(224, BICUBIC) -> RandomHorizontalFlip -> RandAugment()
+
+The workers then only decode.  ``CropAugPlan`` draws the crop boxes, flips and RandAugment ops on
+the host; decoded images of any sizes, both plans and the labels go up in one copy, and
+``sdp_resized_crop`` (csrc/eval.hip) -> ``sdp_randaugment`` (csrc/randaug.hip) ->
+``sdp_train_batch_aug`` produce the model's input.  The uint8 pixels equal Pillow 12.2.0's bit for
+bit (the library torchvision calls for PIL images).  The mapping from RandAugment's (op, magnitude
+bin) to a Pillow call is restated from torchvision's published v2 source; torchvision is not
+installed where this was written, so that mapping is unverified against torchvision itself.
 """
 from __future__ import annotations
 
+import functools
 import math
 from dataclasses import dataclass, field
 from typing import Iterable, List, Optional, Sequence, Tuple
@@ -361,12 +374,388 @@ class TrainBatchTransform:
         return out, (labels_d if labels.is_cuda else labels_d.clone())
 
 
+# ---------------------------------------------------------------------------
+# training: RandomResizedCrop + flip + RandAugment on the device
+# ---------------------------------------------------------------------------
+RRC_SCALE = (0.08, 1.0)          # torchvision RandomResizedCrop defaults
+RRC_RATIO = (3.0 / 4.0, 4.0 / 3.0)
+RRC_ATTEMPTS = 10
+RA_NUM_OPS, RA_MAGNITUDE, RA_BINS = 2, 9, 31   # torchvision RandAugment() defaults
+RA_SIGNED = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness")
+_RA_AFFINE = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate")
+_RA_ENHANCE = ("Brightness", "Color", "Contrast", "Sharpness")
+
+
+@functools.lru_cache(maxsize=None)
+def ra_magnitude(name: str, H: int, W: int, magnitude: int = RA_MAGNITUDE, num_bins: int = RA_BINS) -> float:
+    """The unsigned magnitude torchvision's RandAugment hands to its functional for bin
+    ``magnitude`` of ``num_bins`` on an H x W image (fp32 linspace, as torchvision computes it):
+    the shear tangent, the translation in pixels (before int()), the angle in degrees, m of the
+    enhancers' factor 1 + m, the bits Posterize keeps, Solarize's threshold."""
+    lin = lambda hi: float(torch.linspace(0.0, hi, num_bins)[magnitude])  # noqa: E731
+    if name in ("ShearX", "ShearY"):
+        return lin(0.3)
+    if name == "TranslateX":
+        return lin(150.0 / 331.0 * W)
+    if name == "TranslateY":
+        return lin(150.0 / 331.0 * H)
+    if name == "Rotate":
+        return lin(30.0)
+    if name in _RA_ENHANCE:
+        return lin(0.9)
+    if name == "Posterize":
+        return float(int((8 - (torch.arange(num_bins) / ((num_bins - 1) / 4)).round().int())[magnitude]))
+    if name == "Solarize":
+        return float(255.0 * torch.linspace(1.0, 0.0, num_bins)[magnitude])
+    if name in ("Identity", "AutoContrast", "Equalize"):
+        return 0.0
+    raise ValueError(f"unknown RandAugment op {name!r}")
+
+
+def ra_matrix(name: str, magnitude: float, H: int, W: int) -> Tuple[float, ...]:
+    """The output -> input coefficients Pillow's Image.transform(AFFINE) receives for a geometric op."""
+    m = float(magnitude)
+    if name == "ShearX":
+        return (1.0, m, 0.0, 0.0, 1.0, 0.0)
+    if name == "ShearY":
+        return (1.0, 0.0, 0.0, m, 1.0, 0.0)
+    if name == "TranslateX":
+        return (1.0, 0.0, -float(int(m)), 0.0, 1.0, 0.0)
+    if name == "TranslateY":
+        return (1.0, 0.0, 0.0, 0.0, 1.0, -float(int(m)))
+    if name == "Rotate":  # Image.rotate: entries rounded to 15 digits, translated about (w / 2, h / 2)
+        a = -math.radians(m % 360.0)
+        c, sn = round(math.cos(a), 15), round(math.sin(a), 15)
+        cx, cy = W / 2, H / 2
+        return (c, sn, c * -cx + sn * -cy + 0.0 + cx, -sn, c, -sn * -cx + c * -cy + 0.0 + cy)
+    raise ValueError(name)
+
+
+def ra_words(name: str, magnitude: float, H: int, W: int) -> List[int]:
+    """The eight plan words of one op (layout: include/sdpnet_hip.h), every double-precision step
+    done here.  Raises NotImplementedError where Pillow itself would leave the restated path."""
+    if name not in sp.RA_OPS:
+        raise ValueError(f"unknown RandAugment op {name!r}")
+    w = [sp.RA_OPS.index(name), 0, 0, 0, 0, 0, 0, 0]
+    if name in _RA_AFFINE:
+        m = ra_matrix(name, magnitude, H, W)
+        for x, y in ((0, 0), (W, 0), (0, H), (W, H)):  # Geometry.c check_fixed
+            if not (abs(x * m[0] + y * m[1] + m[2]) < 32768.0 and abs(x * m[3] + y * m[4] + m[5]) < 32768.0):
+                raise NotImplementedError(f"{name}({magnitude}) on {H}x{W}: outside Pillow's 16.16 fixed-point range")
+        fix = lambda v: int(math.floor(v * 65536.0 + 0.5))  # noqa: E731
+        w[1:7] = [fix(m[0]), fix(m[1]), fix(m[2] + m[0] * 0.5 + m[1] * 0.5),
+                  fix(m[3]), fix(m[4]), fix(m[5] + m[3] * 0.5 + m[4] * 0.5)]
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in w[1:7]):
+            raise NotImplementedError(f"{name}({magnitude}) on {H}x{W}: outside Pillow's 16.16 fixed-point range")
+    elif name in _RA_ENHANCE:
+        if name == "Sharpness" and (H < 3 or W < 3):
+            raise NotImplementedError(f"Sharpness on {H}x{W}: ImageFilter.SMOOTH needs H >= 3 and W >= 3")
+        w[1] = int(np.array([1.0 + float(magnitude)], np.float32).view(np.int32)[0])
+    elif name == "Posterize":
+        bits = int(magnitude)
+        if not 0 <= bits <= 8:
+            raise ValueError(f"Posterize keeps 0..8 bits, got {bits}")
+        w[1] = ~(2 ** (8 - bits) - 1) & 0xff
+    elif name == "Solarize":
+        w[1] = min(max(int(math.ceil(float(magnitude))), 0), 256)  # the first v with not (v < threshold)
+    return w
+
+
+@dataclass
+class CropAugPlan:
+    """The per-image random decisions of RandomResizedCrop, RandomHorizontalFlip and RandAugment
+    for one batch of decoded images, as plain host data.
+
+    sizes [B, 2] (H, W of every decoded image), out_size (OH, OW), boxes [B, 4] (top, left, h, w
+    inside the image), flip [B] (0 / 1), ops: per image a list of (op name, magnitude) -- every
+    image the same number (1..4) --, the magnitude signed and meaning what torchvision hands to its
+    functional (``ra_magnitude``).  The ops act on the OH x OW crop."""
+    sizes: np.ndarray
+    out_size: Tuple[int, int]
+    boxes: np.ndarray
+    flip: np.ndarray
+    ops: List[List[Tuple[str, float]]]
+
+    def __post_init__(self):
+        self.sizes = np.asarray(self.sizes, np.int64).reshape(-1, 2)
+        self.boxes = np.asarray(self.boxes, np.int64).reshape(-1, 4)
+        self.flip = np.asarray(self.flip, np.int64).reshape(-1)
+        self.out_size = (int(self.out_size[0]), int(self.out_size[1]))
+        self.ops = [[(str(n), float(m)) for n, m in per] for per in self.ops]
+        self.validate()
+
+    @property
+    def B(self) -> int:
+        return self.sizes.shape[0]
+
+    @property
+    def num_ops(self) -> int:
+        return len(self.ops[0]) if self.ops else RA_NUM_OPS
+
+    @staticmethod
+    def identity(sizes, out_size) -> "CropAugPlan":
+        """The whole image resized, no flip, one Identity op."""
+        sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
+        boxes = np.concatenate([np.zeros_like(sizes), sizes], axis=1)
+        return CropAugPlan(sizes, out_size, boxes, np.zeros(len(sizes), np.int64), [[("Identity", 0.0)] for _ in sizes])
+
+    @staticmethod
+    def from_bins(sizes, out_size, boxes, flip, ops, magnitude: int = RA_MAGNITUDE,
+                  num_bins: int = RA_BINS) -> "CropAugPlan":
+        """Every decision pinned; ops: per image a list of (op name, sign), sign +1 / -1 (ignored
+        by the unsigned ops), the magnitude taken from bin ``magnitude`` of ``num_bins``."""
+        OH, OW = int(out_size[0]), int(out_size[1])
+        full = [[(n, (float(sg) if n in RA_SIGNED else 1.0) * ra_magnitude(n, OH, OW, magnitude, num_bins))
+                 for n, sg in per] for per in ops]
+        return CropAugPlan(sizes, out_size, boxes, flip, full)
+
+    @staticmethod
+    def sample(sizes, out_size, generator: Optional[torch.Generator] = None, num_ops: int = RA_NUM_OPS,
+               magnitude: int = RA_MAGNITUDE, num_bins: int = RA_BINS, scale=RRC_SCALE, ratio=RRC_RATIO,
+               flip_p: float = 0.5) -> "CropAugPlan":
+        """Draw a plan from torch's CPU generator; the same seed gives the same plan.
+
+        RandomResizedCrop (torchvision ``get_params``): up to 10 tries of area = H W U(scale),
+        r = exp(U(log ratio)), w = round(sqrt(area r)), h = round(sqrt(area / r)), the first with
+        0 < w <= W and 0 < h <= H taken with top ~ U{0..H-h}, left ~ U{0..W-w}; else the central
+        crop of the whole width or height clamped to the ratio bounds.  Flip with probability
+        ``flip_p``.  RandAugment (``num_ops`` ops, bin ``magnitude`` of ``num_bins``, NEAREST, fill
+        None): every op uniform over the 14, a signed op negated with probability 0.5.
+
+        The distributions and formulas are torchvision's as published (v2 transforms, restated
+        without torchvision at hand: unverified against torchvision itself); the random stream is
+        not -- the draws of a batch are taken in bulk, a fixed number per image."""
+        sizes = np.asarray(sizes, np.int64).reshape(-1, 2)
+        B = len(sizes)
+        OH, OW = int(out_size[0]), int(out_size[1])
+        if not 1 <= num_ops <= sp.RA_MAX_OPS:
+            raise ValueError(f"num_ops must be 1..{sp.RA_MAX_OPS}, got {num_ops}")
+        c_try, c_op = 3, 3 + 2 * RRC_ATTEMPTS
+        u = torch.rand(B, c_op + 2 * num_ops, generator=generator, dtype=torch.float64).numpy()
+        l0, l1 = math.log(ratio[0]), math.log(ratio[1])
+        boxes = np.zeros((B, 4), np.int64)
+        ops: List[List[Tuple[str, float]]] = []
+        for b, (H, W) in enumerate(sizes.tolist()):
+            area = H * W
+            for a in range(RRC_ATTEMPTS):
+                target = area * (scale[0] + (scale[1] - scale[0]) * u[b, c_try + 2 * a])
+                r = math.exp(l0 + (l1 - l0) * u[b, c_try + 2 * a + 1])
+                w, h = int(round(math.sqrt(target * r))), int(round(math.sqrt(target / r)))
+                if 0 < w <= W and 0 < h <= H:
+                    top = min(int(u[b, 1] * (H - h + 1)), H - h)
+                    left = min(int(u[b, 2] * (W - w + 1)), W - w)
+                    break
+            else:  # central fallback
+                in_ratio = float(W) / float(H)
+                if in_ratio < min(ratio):
+                    w = W
+                    h = int(round(w / min(ratio)))
+                elif in_ratio > max(ratio):
+                    h = H
+                    w = int(round(h * max(ratio)))
+                else:
+                    w, h = W, H
+                top, left = (H - h) // 2, (W - w) // 2
+            boxes[b] = (top, left, h, w)
+            per = []
+            for k in range(num_ops):
+                name = sp.RA_OPS[min(int(u[b, c_op + 2 * k] * len(sp.RA_OPS)), len(sp.RA_OPS) - 1)]
+                m = ra_magnitude(name, OH, OW, magnitude, num_bins)
+                if name in RA_SIGNED and u[b, c_op + 2 * k + 1] <= 0.5:
+                    m = -m
+                per.append((name, m))
+            ops.append(per)
+        return CropAugPlan(sizes, (OH, OW), boxes, (u[:, 0] < flip_p).astype(np.int64), ops)
+
+    def kmax(self) -> int:
+        """The largest tap count of the batch's boxes."""
+        OH, OW = self.out_size
+        return max([1] + [max(_taps(int(w), OW), _taps(int(h), OH)) for _, _, h, w in self.boxes])
+
+    def validate(self) -> None:
+        """Everything the kernels rely on; raises before anything reaches the device."""
+        B = self.B
+        OH, OW = self.out_size
+        if OH <= 0 or OW <= 0:
+            raise ValueError(f"output size {self.out_size}")
+        if self.boxes.shape[0] != B or self.flip.shape[0] != B or len(self.ops) != B:
+            raise ValueError("sizes, boxes, flip and ops must describe the same number of images")
+        if B and not (1 <= self.num_ops <= sp.RA_MAX_OPS and all(len(p) == self.num_ops for p in self.ops)):
+            raise ValueError(f"every image takes the same number of ops, 1..{sp.RA_MAX_OPS}")
+        if not np.isin(self.flip, (0, 1)).all():
+            raise ValueError("flip bits are 0 / 1")
+        for (H, W), (top, left, h, w) in zip(self.sizes.tolist(), self.boxes.tolist()):
+            if H <= 0 or W <= 0:
+                raise ValueError("empty image")
+            if not (0 <= top and 1 <= h and top + h <= H and 0 <= left and 1 <= w and left + w <= W):
+                raise ValueError(f"box {(top, left, h, w)} outside its {H}x{W} image")
+            if h > 100 * w:
+                raise NotImplementedError(f"box {h}x{w}: aspect ratio above 100 (Pillow reorders its passes there)")
+            if w > sp.CROP_MAX_W:
+                raise NotImplementedError(f"box {w} pixels wide (limit {sp.CROP_MAX_W})")
+        if self.kmax() > MAX_TAPS:
+            raise NotImplementedError(f"downscale factor too large ({self.kmax()} taps > {MAX_TAPS})")
+        for per in self.ops:
+            for name, m in per:
+                ra_words(name, m, OH, OW)
+
+    def words(self) -> int:
+        return (sp.CROP_PLAN_PER_IMAGE + sp.RA_PLAN_PER_OP * self.num_ops) * self.B
+
+    def pack(self, out: Optional[np.ndarray] = None, row_origin: bool = False) -> np.ndarray:
+        """int32 words: [B][8] for sdp_resized_crop, then [B][num_ops][8] for sdp_randaugment
+        (layouts: include/sdpnet_hip.h).  ``row_origin``: boxes for images that were cut to the
+        box's rows before packing (top 0)."""
+        if out is None:
+            out = np.empty(self.words(), np.int32)
+        out[:] = 0
+        B, n = self.B, sp.CROP_PLAN_PER_IMAGE * self.B
+        crop = out[:n].reshape(B, sp.CROP_PLAN_PER_IMAGE)
+        crop[:, 0:4] = self.boxes
+        if row_origin:
+            crop[:, 0] = 0
+        crop[:, 4] = self.flip
+        OH, OW = self.out_size
+        ra = out[n:].reshape(B, self.num_ops, sp.RA_PLAN_PER_OP) if B else out[n:]
+        for b, per in enumerate(self.ops):
+            for k, (name, m) in enumerate(per):
+                ra[b, k] = np.array(ra_words(name, m, OH, OW), np.int64).astype(np.int32)
+        return out
+
+
+class TrainImageTransform:
+    """The reference's whole ``train_transforms`` plus its collate on decoded images:
+    ``__call__(images, labels, crop_plan=None, plan=None) -> (images [B, 3, OH, OW] of ``dtype`` on
+    ``device``, targets)``.  targets as for ``TrainBatchTransform``.
+
+    images: a sequence of decoded images (PIL, ndarray or uint8 tensor, HWC) of any sizes; labels:
+    int64 [B] (a tensor on either side, or a sequence of ints).  The rows of every image that its
+    crop box covers, both plans, the image table and the host labels are packed into one of two
+    alternating pinned buffers and uploaded with one copy; the only host wait is on the copy out
+    of that buffer two batches earlier.  Then sdp_resized_crop -> sdp_randaugment (in place) ->
+    sdp_train_batch_aug.  The flip happens in the crop kernel (``flip_p``), so the ``AugPlan``
+    drawn here has no flips."""
+
+    def __init__(self, image_size=(224, 224), num_classes: int = 1000, mean=IMAGENET_MEAN, std=IMAGENET_STD,
+                 device="cuda", dtype=torch.float32, mix: Optional[str] = "reference", erase_p: float = 0.25,
+                 flip_p: float = 0.5, num_ops: int = RA_NUM_OPS, magnitude: int = RA_MAGNITUDE,
+                 num_magnitude_bins: int = RA_BINS, scale=RRC_SCALE, ratio=RRC_RATIO,
+                 generator: Optional[torch.Generator] = None):
+        self.image_size = (int(image_size[0]), int(image_size[1]))
+        self.num_classes = int(num_classes)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("TrainImageTransform runs sdp_resized_crop / sdp_randaugment / sdp_train_batch_aug; "
+                               "the HIP path has no CPU fallback")
+        sp.dcode(dtype)
+        self.dtype = dtype
+        self.mix, self.erase_p, self.flip_p = mix, float(erase_p), float(flip_p)
+        self.num_ops, self.magnitude, self.num_magnitude_bins = int(num_ops), int(magnitude), int(num_magnitude_bins)
+        self.scale, self.ratio = tuple(scale), tuple(ratio)
+        self.generator = generator
+        self.lut = normalize_lut(mean, std).to(self.device)
+        self._staging = (_Staging(), _Staging())
+        self._turn = 0
+
+    def sample_crop(self, sizes) -> CropAugPlan:
+        return CropAugPlan.sample(sizes, self.image_size, self.generator, self.num_ops, self.magnitude,
+                                  self.num_magnitude_bins, self.scale, self.ratio, self.flip_p)
+
+    def sample_batch(self, B: int) -> AugPlan:
+        return AugPlan.sample(B, *self.image_size, self.generator, self.mix, self.erase_p, 0.0)
+
+    def sample(self, sizes) -> Tuple[CropAugPlan, AugPlan]:
+        """Both plans of one batch, drawn in the order ``__call__`` draws them."""
+        crop = self.sample_crop(sizes)
+        return crop, self.sample_batch(crop.B)
+
+    def __call__(self, images: Sequence, labels, crop_plan: Optional[CropAugPlan] = None,
+                 plan: Optional[AugPlan] = None):
+        arrs = [_as_rgb_u8(im) for im in images]
+        B = len(arrs)
+        OH, OW = self.image_size
+        labels = torch.as_tensor(labels).to(torch.int64)
+        if labels.shape != (B,):
+            raise ValueError(f"labels must be [B] = [{B}], got {tuple(labels.shape)}")
+        if B == 0:
+            return torch.empty(0, 3, OH, OW, dtype=self.dtype, device=self.device), labels.to(self.device)
+        sizes = np.array([a.shape[:2] for a in arrs], np.int64)
+        if crop_plan is None:
+            crop_plan = self.sample_crop(sizes)
+        if crop_plan.out_size != self.image_size or not np.array_equal(crop_plan.sizes, sizes):
+            raise ValueError("crop_plan was made for other image sizes or another output size")
+        if plan is None:
+            plan = self.sample_batch(B)
+        if (plan.B, plan.H, plan.W) != (B, OH, OW):
+            raise ValueError(f"plan is for {(plan.B, plan.H, plan.W)}, the batch is {(B, OH, OW)}")
+        if not labels.is_cuda and not (0 <= int(labels.min()) and int(labels.max()) < self.num_classes):
+            raise ValueError(f"label outside [0, {self.num_classes})")
+        # only the rows under a box travel: image b becomes its rows [top, top + h), full width
+        boxes = crop_plan.boxes
+        hw = np.stack([boxes[:, 2], sizes[:, 1]], axis=1)
+        nbytes = hw[:, 0] * hw[:, 1] * 3
+        offs = np.zeros(B, np.int64)
+        offs[1:] = np.cumsum(nbytes)[:-1]
+        # one pinned buffer: crop + RandAugment plan | batch plan | offs | hw | host labels | pixels
+        n_crop, n_plan = 4 * crop_plan.words(), 4 * plan.words()
+        o_plan = _round_up(n_crop, 16)
+        o_offs = _round_up(o_plan + n_plan, 16)
+        o_hw = _round_up(o_offs + 8 * B, 16)
+        o_lab = _round_up(o_hw + 8 * B, 16)
+        o_img = _round_up(o_lab + (0 if labels.is_cuda else 8 * B), 16)
+        n_img = int(nbytes.sum())
+        st = self._staging[self._turn]
+        self._turn ^= 1
+        host = st.take(o_img + n_img)
+        hv = host.numpy()
+        crop_plan.pack(hv[:n_crop].view(np.int32), row_origin=True)
+        plan.pack(hv[o_plan:o_plan + n_plan].view(np.int32))
+        hv[o_offs:o_offs + 8 * B].view(np.int64)[:] = offs
+        hv[o_hw:o_hw + 8 * B].view(np.int32)[:] = hw.astype(np.int32).reshape(-1)
+        if not labels.is_cuda:
+            hv[o_lab:o_lab + 8 * B].view(np.int64)[:] = labels.numpy()
+        for a, (top, _, h, _), o, n in zip(arrs, boxes.tolist(), offs.tolist(), nbytes.tolist()):
+            hv[o_img + o:o_img + o + n].reshape(h, a.shape[1], 3)[:] = a[top:top + h]
+        with torch.cuda.device(self.device):
+            dev = host.to(self.device, non_blocking=True)
+            st.event = torch.cuda.Event()
+            st.event.record()
+            n_box = 4 * sp.CROP_PLAN_PER_IMAGE * B
+            crop_d = dev[:n_box].view(torch.int32)
+            ra_d = dev[n_box:n_crop].view(torch.int32)
+            plan_d = dev[o_plan:o_plan + n_plan].view(torch.int32)
+            offs_d = dev[o_offs:o_offs + 8 * B].view(torch.int64)
+            hw_d = dev[o_hw:o_hw + 8 * B].view(torch.int32).view(B, 2)
+            labels_d = labels if labels.is_cuda else dev[o_lab:o_lab + 8 * B].view(torch.int64)
+            pix_d = dev[o_img:o_img + n_img]
+            max_h, max_w = int(boxes[:, 2].max()), int(boxes[:, 3].max())
+            rows = np.concatenate([np.zeros((B, 1), np.int64), boxes[:, 1:]], axis=1)
+            u8 = sp.resized_crop(pix_d, offs_d, hw_d, crop_d, self.image_size, crop_plan.kmax(), max_h, max_w,
+                                 host=(offs, hw, rows))
+            sp.randaugment(u8, ra_d, crop_plan.num_ops)
+            mixed = plan.mode != MODE_NONE
+            out, targets = sp.train_batch_aug(u8, labels_d, self.lut, plan_d, self.num_classes, self.dtype, mixed,
+                                              channels_last=True)
+        if mixed:
+            return out, targets
+        return out, (labels_d if labels.is_cuda else labels_d.clone())
+
+
+def train_transforms(image_size=(224, 224), mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda",
+                     dtype=torch.float32, **kw) -> TrainImageTransform:
+    """hf_dataset_generator.py:43-57 signature; returns the batched device transform (which also
+    does the collate's CutMix / MixUp; ``mix=None`` leaves the int64 labels)."""
+    return TrainImageTransform(image_size, mean=mean, std=std, device=device, dtype=dtype, **kw)
+
+
 class DeviceAugLoader:
     """Wraps a loader of (uint8 images, int labels) host batches into an iterable of
     (images, targets) device batches: drops into ``Trainer(train_data=...)`` (its ``.to(gpu_id)``
-    on the batches is then a no-op; ``len()`` and ``.sampler`` are the loader's)."""
+    on the batches is then a no-op; ``len()`` and ``.sampler`` are the loader's).  With a
+    ``TrainImageTransform`` the loader yields (list of decoded images, labels) instead, i.e. its
+    ``collate_fn`` returns lists."""
 
-    def __init__(self, loader, transform: TrainBatchTransform):
+    def __init__(self, loader, transform):
         self.loader = loader
         self.transform = transform
 

@@ -12,6 +12,7 @@ There is no fallback: if the shared library is missing or cannot be loaded,
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 import struct
 from dataclasses import dataclass
@@ -154,6 +155,9 @@ _SIGS = {
     "sdp_attn_dropout_mask": ([_vp, _i32, _i32, _f32, _u64, _vp], _i32),
     # training input (augment.hip)
     "sdp_train_batch_aug": ([_vp, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp], _i32),
+    # training input: crop / flip (eval.hip) and RandAugment (randaug.hip)
+    "sdp_resized_crop": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp], _i32),
+    "sdp_randaugment": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
 }
 
 _lib = None
@@ -1500,3 +1504,104 @@ def train_batch_aug(images: torch.Tensor, labels: Optional[torch.Tensor], lut: t
                                    targets.stride(0) if (mixed and B > 1) else K, K, _stream(out))
     _check(rc, "train_batch_aug")
     return out, targets
+
+
+# ---------------------------------------------------------------------------
+# training input: RandomResizedCrop + flip (eval.hip), RandAugment (randaug.hip)
+# ---------------------------------------------------------------------------
+CROP_PLAN_PER_IMAGE = 8   # int32 words per image: {top, left, h, w, flip, 0, 0, 0}
+RA_PLAN_PER_OP = 8        # int32 words per op: {op, p1 .. p7}
+RA_MAX_OPS = 4
+RA_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
+          "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")   # op code = index
+CROP_MAX_TAPS = 160
+CROP_MAX_W = 40960
+
+
+def resized_crop_ws_words(B: int, out_size, kmax: int) -> int:
+    """int32 words of sdp_resized_crop's tap-table workspace."""
+    return B * (out_size[0] + out_size[1]) * (2 + kmax)
+
+
+def resized_crop(pix: torch.Tensor, offs: torch.Tensor, hw: torch.Tensor, plan: torch.Tensor, out_size, kmax: int,
+                 max_h: int, max_w: int, ws: Optional[torch.Tensor] = None, tmp: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, host=None) -> torch.Tensor:
+    """RandomResizedCrop + flip of a packed batch of decoded images (sdp_resized_crop).
+
+    pix uint8 (packed HWC images), offs int64 [B], hw int32 [B, 2], plan int32 [>= 8 B] (layout:
+    include/sdpnet_hip.h), all on the device.  ``kmax``: the largest tap count of the batch; ``max_h``
+    / ``max_w``: the tallest / widest box.  ``ws`` (int32, >= resized_crop_ws_words) and ``tmp``
+    (uint8, >= B * max_h * OW * 4) are the caller's workspace, allocated here when None.  ``host``:
+    the same (offs, hw, boxes [B, 4] = top, left, h, w) as host arrays; when given, every image is
+    checked to lie inside pix, every box inside its image and under (max_h, max_w), and kmax to
+    cover every box, before the launch.  Returns out uint8 [B, OH, OW, 3] (``out`` itself when given)."""
+    _need_cuda(pix, offs, hw, plan, ws, tmp, out)
+    _req(pix.dtype == torch.uint8 and pix.dim() == 1 and pix.is_contiguous(), "resized_crop pix uint8 [n]")
+    _req(hw.dtype == torch.int32 and hw.dim() == 2 and hw.shape[1] == 2 and hw.is_contiguous(), "resized_crop hw")
+    B = hw.shape[0]
+    _req(offs.dtype == torch.int64 and tuple(offs.shape) == (B,) and offs.is_contiguous(), "resized_crop offs int64 [B]")
+    _req(plan.dtype == torch.int32 and plan.is_contiguous() and plan.numel() >= CROP_PLAN_PER_IMAGE * B,
+         "resized_crop plan int32 [B, 8]")
+    OH, OW = int(out_size[0]), int(out_size[1])
+    kmax, max_h, max_w = int(kmax), int(max_h), int(max_w)
+    _req(OH > 0 and OW > 0 and 0 < kmax <= CROP_MAX_TAPS and max_h > 0 and 0 < max_w <= CROP_MAX_W,
+         "resized_crop sizes")
+    if host is not None:
+        offs_h, hw_h, boxes_h = host
+        _req(len(offs_h) == B and len(hw_h) == B and len(boxes_h) == B, "resized_crop host arrays")
+        for o, (H, W), (top, left, h, w) in zip(offs_h, hw_h, boxes_h):
+            o, H, W, top, left, h, w = (int(v) for v in (o, H, W, top, left, h, w))
+            _req(H > 0 and W > 0 and 0 <= o and o + H * W * 3 <= pix.numel(), "resized_crop image outside pix")
+            _req(0 <= top and 1 <= h <= max_h and top + h <= H and 0 <= left and 1 <= w <= max_w and left + w <= W,
+                 "resized_crop box outside its image")
+            _req(h <= 100 * w, "resized_crop box aspect ratio above 100")
+            _req(max(math.ceil(2.0 * max(1.0, w / OW)), math.ceil(2.0 * max(1.0, h / OH))) * 2 + 1 <= kmax,
+                 "resized_crop kmax below a box's tap count")
+    dev = pix.device
+    tmp_stride = max_h * OW * 4
+    if ws is None:
+        ws = torch.empty(resized_crop_ws_words(B, (OH, OW), kmax), dtype=torch.int32, device=dev)
+    if tmp is None:
+        tmp = torch.empty(max(1, B * tmp_stride), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(B, OH, OW, 3, dtype=torch.uint8, device=dev)
+    _req(ws.dtype == torch.int32 and ws.is_contiguous() and ws.numel() >= resized_crop_ws_words(B, (OH, OW), kmax),
+         "resized_crop ws")
+    _req(tmp.dtype == torch.uint8 and tmp.is_contiguous() and tmp.numel() >= B * tmp_stride, "resized_crop tmp")
+    _req(out.dtype == torch.uint8 and tuple(out.shape) == (B, OH, OW, 3) and out.is_contiguous(),
+         "resized_crop out uint8 [B, OH, OW, 3]")
+    rc = lib().sdp_resized_crop(pix.data_ptr(), offs.data_ptr(), hw.data_ptr(), plan.data_ptr(), B, OH, OW, kmax,
+                                ws.data_ptr(), tmp.data_ptr(), tmp_stride, max_w, out.data_ptr(), _stream(out))
+    _check(rc, "resized_crop")
+    return out
+
+
+def randaugment(images: torch.Tensor, plan: torch.Tensor, num_ops: int, scratch: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``num_ops`` RandAugment ops per image on a uint8 batch [B, H, W, 3] (sdp_randaugment).
+
+    plan int32 [>= B * num_ops * 8] on the device (layout: include/sdpnet_hip.h; the host builds and
+    validates it, preprocess.CropAugPlan).  ``scratch``: the caller's workspace, uint8 with at least
+    images.numel() elements (allocated here when None).  ``out``: uint8 [B, H, W, 3]; None works in
+    place.  Returns the tensor that holds the result."""
+    _need_cuda(images, plan, scratch, out)
+    _req(images.dtype == torch.uint8 and images.dim() == 4 and images.shape[3] == 3 and images.is_contiguous(),
+         "randaugment images uint8 [B, H, W, 3]")
+    B, H, W, _ = images.shape
+    num_ops = int(num_ops)
+    _req(1 <= num_ops <= RA_MAX_OPS, "randaugment num_ops in 1..4")
+    _req(H > 0 and W > 0 and H * W * 3 < 2 ** 31, "randaugment image size")
+    _req(plan.dtype == torch.int32 and plan.is_contiguous() and plan.numel() >= B * num_ops * RA_PLAN_PER_OP,
+         "randaugment plan int32 [B, num_ops, 8]")
+    if out is None:
+        out = images
+    _req(out.dtype == torch.uint8 and tuple(out.shape) == tuple(images.shape) and out.is_contiguous(),
+         "randaugment out uint8 [B, H, W, 3]")
+    if scratch is None:
+        scratch = torch.empty(max(1, images.numel()), dtype=torch.uint8, device=images.device)
+    _req(scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.numel() >= images.numel(),
+         "randaugment scratch")
+    rc = lib().sdp_randaugment(images.data_ptr(), out.data_ptr(), plan.data_ptr(), B, H, W, num_ops,
+                               scratch.data_ptr(), _stream(out))
+    _check(rc, "randaugment")
+    return out
