@@ -853,6 +853,63 @@ int sdp_resized_crop(const uint8_t* pix, const int64_t* offs, const int* hw, con
 int sdp_randaugment(const uint8_t* in, uint8_t* out, const int32_t* plan, int B, int H, int W, int num_ops,
                     uint8_t* scratch, void* stream);
 
+/* ---- hybrid JPEG decode: Huffman on the host, reconstruction on the device ----
+ * Streams taken: SOF0, or SOF1 with Huffman coding; 8-bit samples, 8-bit quantisation tables; one
+ * component, or three read as YCbCr (refused when an Adobe APP14 segment says transform 0 or the
+ * component ids spell "RGB"); one scan; luma sampling 1x1, 2x1 or 2x2 over chroma 1x1; DRI / RSTn;
+ * FF00 stuffing and FF fill bytes.  Anything else is reported, never approximated.
+ *
+ * Return codes of the two host calls: 0 taken; > 0 a well-formed JPEG outside the subset (1
+ * progressive, 2 arithmetic coding, 3 12-bit samples / 16-bit tables, 4 component count, 5
+ * sampling, 6 several scans, 7 DNL, 8 not YCbCr, 9 lossless / hierarchical, 10 more than 2^31 - 1
+ * coefficients) -- decode it elsewhere; < 0 malformed (-1 truncated, -2 syntax, -3 a code not in
+ * its table, -4 coefficient index past 63, -5 DC category above 11 / AC category above 10 / DC
+ * outside int16, -6 a table never defined, -7 restart marker wrong or missing, -8 no EOI after the
+ * last MCU, -9 coef_cap too small, -10 bad argument).
+ *
+ * info: int32 [16] = {W, H, components (1 | 3), mode (0: 1x1 or grey, 1: 2x1, 2: 2x2), then
+ * (blocks wide, blocks high) of components 0, 1, 2 over the padded MCU raster (0 when absent), the
+ * number of int16 coefficients (64 per block), the restart interval, MCU columns, MCU rows, 0, 0}.
+ * A single-component scan is not interleaved: its grid is ceil(W / 8) x ceil(H / 8) whatever
+ * sampling factors the frame header carries.
+ *
+ * Both calls are plain C++ (csrc/jpeg_host.h): no HIP call, no global state, no allocation; any
+ * number of threads may call them at once.  No byte at or beyond data + len is read, no element at
+ * or beyond coef + coef_cap written, and the work is O(len) whatever the header claims. */
+
+/* Parses SOI .. SOS only (no entropy data is looked at). */
+int sdp_jpeg_probe(const uint8_t* data, int64_t len, int32_t* info);
+
+/* Writes the quantised coefficients: component-major, the blocks of a component in raster order
+ * over its padded grid, 64 values per block in natural (row-major) order; info[10] of them.
+ * qt: uint8 [3][64], the table of component c in natural order (zero for absent components).
+ * On a non-zero return coef, qt and info hold no usable result. */
+int sdp_jpeg_entropy_decode(const uint8_t* data, int64_t len, int16_t* coef, int64_t coef_cap, uint8_t* qt,
+                            int32_t* info);
+
+/* Dequantisation, inverse DCT, chroma upsampling and colour conversion of B images of any sizes
+ * and modes: out = np.asarray(PIL.Image.open(file).convert("RGB")), HWC uint8 (a grey image's
+ * plane in all three channels), bit for bit with Pillow 12.2.0 (libjpeg's jidctint / "fancy"
+ * upsampling / jdcolor arithmetic restated): DESCALE(x, n) = (x + (1 << (n - 1))) >> n; columns
+ * first, descaled by 11, rows descaled by 18, + 128, clamped; 2:1 chroma filtered 3:1 (h) or
+ * 9:3:3:1 (h and v) with the edges of the component's true size ceil(W / 2) [x ceil(H / 2)], a
+ * component at most 2 samples wide replicated; R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130
+ * cb + 32768) >> 16), G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), clamped.  Bit-exactness holds
+ * where the signed 32-bit computation does not overflow, which covers every stream an 8-bit encoder
+ * produces; beyond it sums and products wrap (unsigned arithmetic), nothing is undefined.
+ *   desc: int32 [B][64] per image {W, H, components, mode, MCU columns, MCU rows, coefficient
+ *   offset (int64 in int16 elements, low word first, a multiple of 8), workspace offset (int64,
+ *   bytes, a multiple of 8), pixel offset (int64, bytes), 0, 0, 0, 0, then the 192 bytes of qt}.
+ *   desc_host and desc_dev are the same words on either side (one upload).  Before any launch the
+ *   host copy is checked: sizes 1..65535, MCU counts that follow from them, and for every image
+ *   [coef offset, + 64 blocks) inside coef_elems, [ws offset, + 64 blocks) inside ws_bytes,
+ *   [pixel offset, + 3 W H) inside pix_bytes; otherwise hipErrorInvalidValue and nothing is written.
+ *   Ranges of different images must not overlap (not checked).
+ *   coef: 16-byte aligned; ws: 8-byte aligned planar uint8 samples over the padded grids, as many
+ *   bytes per image as it has coefficients.  B <= 65535; B == 0 is a no-op. */
+int sdp_jpeg_reconstruct(const int16_t* coef, int64_t coef_elems, const int32_t* desc_host, const int32_t* desc_dev,
+                         int B, uint8_t* ws, int64_t ws_bytes, uint8_t* pix, int64_t pix_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

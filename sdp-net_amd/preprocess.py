@@ -36,11 +36,22 @@ the host; decoded images of any sizes, both plans and the labels go up in one co
 bit (the library torchvision calls for PIL images).  The mapping from RandAugment's (op, magnitude
 bin) to a Pillow call is restated from torchvision's published v2 source; torchvision is not
 installed where this was written, so that mapping is unverified against torchvision itself.
+
+Decode itself is hybrid (``JpegDecoder``): every transform above also takes encoded JPEGs (``bytes``
+/ ``bytearray`` / ``memoryview`` items).  The serial Huffman decode runs on a host thread pool
+(``sdp_jpeg_entropy_decode``, plain C++, the GIL released); the quantised coefficients go up in one
+copy and ``sdp_jpeg_reconstruct`` (csrc/jpeg.hip) dequantises, inverts the DCT, upsamples the chroma
+and converts the colours straight into the packed ``pix / offs / hw`` buffer the kernels above read:
+the decoded pixels never exist on the host.  The pixels equal ``Image.open(f).convert("RGB")`` of
+Pillow 12.2.0 bit for bit; a JPEG outside the subset (progressive, CMYK, ...) is decoded by Pillow
+and placed into the same buffer; a malformed one raises.
 """
 from __future__ import annotations
 
 import functools
+import io
 import math
+from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass, field
 from typing import Iterable, List, Optional, Sequence, Tuple
 
@@ -76,6 +87,148 @@ def _taps(n_in: int, n_out: int) -> int:
     return int(math.ceil(2.0 * max(1.0, n_in / n_out))) * 2 + 1
 
 
+def _is_encoded(img) -> bool:
+    return isinstance(img, (bytes, bytearray, memoryview))
+
+
+class JpegDecoder:
+    """Hybrid JPEG decode of a batch: ``decode(items) -> (pix, offs, hw)`` on ``device``, the packed
+    triple sdp_val_preprocess and sdp_resized_crop read (pix uint8 [sum 3 H W], offs int64 [B], hw
+    int32 [B, 2]).
+
+    Every encoded item is probed (markers only).  The supported ones are Huffman-decoded on a pool
+    of ``num_threads`` host threads (at most 16) into one pinned buffer, which goes up in one copy
+    together with the descriptors, and one ``sdp_jpeg_reconstruct`` call writes their pixels.  An
+    unsupported item (progressive, CMYK, ...) is decoded by Pillow and travels as pixels in the same
+    upload, as does an item that is already decoded (PIL image, ndarray, tensor), so the batch is
+    always complete and in order.  A malformed item raises ``ValueError`` naming its index before
+    anything is uploaded."""
+
+    MAX_THREADS = 16
+
+    def __init__(self, device="cuda", num_threads: int = 8):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("JpegDecoder runs sdp_jpeg_reconstruct; the HIP path has no CPU fallback")
+        self.num_threads = max(1, min(int(num_threads), self.MAX_THREADS))
+        self._pool = ThreadPoolExecutor(self.num_threads) if self.num_threads > 1 else None
+        self._staging = (_Staging(), _Staging())
+        self._turn = 0
+        self.last_fallbacks: List[int] = []   # indices of the last batch that Pillow decoded
+
+    @staticmethod
+    def _pillow(data) -> np.ndarray:
+        from PIL import Image
+        return _as_rgb_u8(Image.open(io.BytesIO(bytes(data))))
+
+    def decode(self, items: Sequence) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return self.decode_with_host(items)[:3]
+
+    def decode_with_host(self, items: Sequence):
+        """``decode`` plus the host copies of offs (int64 [B]) and hw (int64 [B, 2])."""
+        B = len(items)
+        if B == 0:
+            z = torch.empty(0, dtype=torch.uint8, device=self.device)
+            return (z, torch.empty(0, dtype=torch.int64, device=self.device),
+                    torch.empty(0, 2, dtype=torch.int32, device=self.device), np.zeros(0, np.int64),
+                    np.zeros((0, 2), np.int64))
+        infos: List[Optional[np.ndarray]] = [None] * B
+        arrs: List[Optional[np.ndarray]] = [None] * B
+        self.last_fallbacks = []
+        for i, it in enumerate(items):
+            if not _is_encoded(it):
+                arrs[i] = _as_rgb_u8(it)
+                continue
+            rc, info = sp.jpeg_probe(it)
+            if rc < 0:
+                raise ValueError(f"item {i}: malformed JPEG ({sp.JPEG_MALFORMED.get(rc, rc)})")
+            if rc > 0:
+                try:
+                    arrs[i] = self._pillow(it)
+                except Exception as e:
+                    raise ValueError(f"item {i}: malformed JPEG ({e})") from e
+                self.last_fallbacks.append(i)
+            else:
+                infos[i] = info
+        hw = np.array([(a.shape[0], a.shape[1]) if a is not None else (int(f[1]), int(f[0]))
+                       for a, f in zip(arrs, infos)], np.int64)
+        if (hw <= 0).any():
+            raise ValueError("empty image")
+        nbytes = hw[:, 0] * hw[:, 1] * 3
+        offs = np.zeros(B, np.int64)
+        offs[1:] = np.cumsum(nbytes)[:-1]
+        n_pix = int(nbytes.sum())
+        jpegs = [i for i in range(B) if infos[i] is not None]
+        ncoef = np.array([_round_up(int(infos[i][10]), 64) for i in jpegs], np.int64)
+        coef_off = np.zeros(len(jpegs), np.int64)
+        coef_off[1:] = np.cumsum(ncoef)[:-1]
+        n_coef = int(ncoef.sum())
+        # one pinned buffer: descriptors | offs | hw | coefficients | pixels of the items decoded on the host
+        W = sp.JPEG_DESC_WORDS
+        n_desc = 4 * W * len(jpegs)
+        o_offs = _round_up(n_desc, 16)
+        o_hw = _round_up(o_offs + 8 * B, 16)
+        o_coef = _round_up(o_hw + 8 * B, 16)
+        o_raw = _round_up(o_coef + 2 * n_coef, 16)
+        raw = [i for i in range(B) if arrs[i] is not None]
+        raw_off = np.zeros(len(raw), np.int64)
+        raw_off[1:] = np.cumsum(nbytes[raw])[:-1]
+        total = o_raw + int(nbytes[raw].sum())
+        st = self._staging[self._turn]
+        self._turn ^= 1
+        host = st.take(total)
+        hv = host.numpy()
+        desc = hv[:n_desc].view(np.int32)
+        desc[:] = 0
+        hv[o_offs:o_offs + 8 * B].view(np.int64)[:] = offs
+        hv[o_hw:o_hw + 8 * B].view(np.int32)[:] = hw.astype(np.int32).reshape(-1)
+        coef = hv[o_coef:o_coef + 2 * n_coef].view(np.int16)
+
+        def job(k: int) -> int:
+            i = jpegs[k]
+            d = desc[k * W:(k + 1) * W]
+            rc, info = sp.jpeg_entropy_decode(items[i], coef[coef_off[k]:coef_off[k] + ncoef[k]],
+                                              d[sp.JPEG_DESC_QT:].view(np.uint8))
+            if rc == 0:  # the planar samples of an image take as many bytes as it has coefficients
+                sp.jpeg_fill_desc(d, info, coef_off[k], coef_off[k], offs[i])
+            return rc
+
+        codes = list(self._pool.map(job, range(len(jpegs)))) if self._pool is not None and len(jpegs) > 1 \
+            else [job(k) for k in range(len(jpegs))]
+        for k, rc in enumerate(codes):
+            if rc < 0:
+                raise ValueError(f"item {jpegs[k]}: malformed JPEG ({sp.JPEG_MALFORMED.get(rc, rc)})")
+        late = [jpegs[k] for k, rc in enumerate(codes) if rc > 0]
+        if late:  # unsupported only behind the scan (a second scan, DNL): Pillow takes them, the batch is redone
+            items = list(items)
+            for i in late:
+                try:
+                    items[i] = self._pillow(items[i])
+                except Exception as e:
+                    raise ValueError(f"item {i}: malformed JPEG ({e})") from e
+            first = self.last_fallbacks
+            out = self.decode_with_host(items)
+            self.last_fallbacks = sorted(first + late)
+            return out
+        for i, o in zip(raw, raw_off.tolist()):
+            hv[o_raw + o:o_raw + o + nbytes[i]] = np.ascontiguousarray(arrs[i]).reshape(-1)
+        with torch.cuda.device(self.device):
+            dev = host.to(self.device, non_blocking=True)
+            st.event = torch.cuda.Event()
+            st.event.record()
+            offs_d = dev[o_offs:o_offs + 8 * B].view(torch.int64).clone()  # copies: the upload can then go
+            hw_d = dev[o_hw:o_hw + 8 * B].view(torch.int32).view(B, 2).clone()
+            if not jpegs:  # nothing to reconstruct: the uploaded pixels are the batch
+                return dev[o_raw:o_raw + n_pix], offs_d, hw_d, offs, hw
+            pix = torch.empty(n_pix, dtype=torch.uint8, device=self.device)
+            ws = torch.empty(n_coef, dtype=torch.uint8, device=self.device)
+            sp.jpeg_reconstruct(dev[o_coef:o_coef + 2 * n_coef].view(torch.int16), desc, dev[:n_desc].view(torch.int32),
+                                len(jpegs), ws, pix)
+            for i, o in zip(raw, raw_off.tolist()):
+                pix[offs[i]:offs[i] + nbytes[i]] = dev[o_raw + o:o_raw + o + nbytes[i]]
+        return pix, offs_d, hw_d, offs, hw
+
+
 class ValTransform:
     """Batched ``val_transforms(image_size, crop_size, mean, std)``:
     ``__call__(images) -> Tensor[B, 3, crop_h, crop_w]`` on ``device``."""
@@ -92,8 +245,33 @@ class ValTransform:
         self.mean, self.std = tuple(mean), tuple(std)
         self.device = torch.device(device)
         self.dtype = dtype
+        self.jpeg_decoder: Optional[JpegDecoder] = None  # made on the first batch that holds encoded JPEGs
+
+    def _jpeg(self) -> JpegDecoder:
+        if self.jpeg_decoder is None:
+            self.jpeg_decoder = JpegDecoder(self.device)
+        return self.jpeg_decoder
+
+    def _call_encoded(self, images: Sequence, return_u8: bool):
+        """A batch with encoded JPEGs in it: decoded on the device into the packed triple."""
+        pix, offs_d, hw_d, _, hw = self._jpeg().decode_with_host(images)
+        RH, RW = self.image_size
+        kmax = 1
+        for H, W in hw.tolist():
+            if H > 100 * W:
+                raise NotImplementedError(f"image {H}x{W}: aspect ratio above 100 (Pillow reorders its passes there)")
+            kmax = max(kmax, _taps(W, RW), _taps(H, RH))
+        if kmax > MAX_TAPS:
+            raise NotImplementedError(f"downscale factor too large ({kmax} taps > {MAX_TAPS})")
+        tmp_stride = int(hw[:, 0].max()) * self.crop_size[1] * 4
+        out, u8 = sp.val_preprocess(pix, offs_d, hw_d, self.image_size, self.crop_size, self.top, self.left, kmax,
+                                    self.mean, self.std, tmp_stride, self.dtype, want_u8=return_u8,
+                                    max_w=int(hw[:, 1].max()))
+        return (out, u8) if return_u8 else out
 
     def __call__(self, images: Sequence, return_u8: bool = False):
+        if any(_is_encoded(im) for im in images):
+            return self._call_encoded(images, return_u8)
         arrs = [_as_rgb_u8(im) for im in images]
         B = len(arrs)
         RH, RW = self.image_size
@@ -139,7 +317,8 @@ def val_transforms(image_size=(320, 320), crop_size=(224, 224), mean=IMAGENET_ME
 def batches(dataset: Iterable, transform: ValTransform, batch_size: int = 256) -> Iterable[Tuple[torch.Tensor, torch.Tensor]]:
     """(images, labels) device batches from an iterable of (decoded image, int label)
     pairs -- the hf_dataset + DataLoader(batch_size=256, shuffle=False) of
-    model_test.py:52-53 with the transform moved onto the GPU."""
+    model_test.py:52-53 with the transform moved onto the GPU.  An image may also be an encoded
+    JPEG (bytes / bytearray / memoryview): the transform then decodes the batch on the device."""
     imgs: List = []
     labels: List[int] = []
     for img, lab in dataset:
@@ -656,6 +835,7 @@ class TrainImageTransform:
         self.lut = normalize_lut(mean, std).to(self.device)
         self._staging = (_Staging(), _Staging())
         self._turn = 0
+        self.jpeg_decoder: Optional[JpegDecoder] = None  # made on the first batch that holds encoded JPEGs
 
     def sample_crop(self, sizes) -> CropAugPlan:
         return CropAugPlan.sample(sizes, self.image_size, self.generator, self.num_ops, self.magnitude,
@@ -669,8 +849,64 @@ class TrainImageTransform:
         crop = self.sample_crop(sizes)
         return crop, self.sample_batch(crop.B)
 
+    def _call_encoded(self, images: Sequence, labels, crop_plan: Optional[CropAugPlan], plan: Optional[AugPlan]):
+        """A batch with encoded JPEGs in it: the whole images are decoded on the device (one upload of
+        coefficients), the plans and host labels follow in a second, small upload, and the same three
+        kernels run with the boxes in whole-image coordinates."""
+        B = len(images)
+        OH, OW = self.image_size
+        labels = torch.as_tensor(labels).to(torch.int64)
+        if labels.shape != (B,):
+            raise ValueError(f"labels must be [B] = [{B}], got {tuple(labels.shape)}")
+        if self.jpeg_decoder is None:
+            self.jpeg_decoder = JpegDecoder(self.device)
+        pix_d, offs_d, hw_d, offs, sizes = self.jpeg_decoder.decode_with_host(images)
+        if crop_plan is None:
+            crop_plan = self.sample_crop(sizes)
+        if crop_plan.out_size != self.image_size or not np.array_equal(crop_plan.sizes, sizes):
+            raise ValueError("crop_plan was made for other image sizes or another output size")
+        if plan is None:
+            plan = self.sample_batch(B)
+        if (plan.B, plan.H, plan.W) != (B, OH, OW):
+            raise ValueError(f"plan is for {(plan.B, plan.H, plan.W)}, the batch is {(B, OH, OW)}")
+        if not labels.is_cuda and not (0 <= int(labels.min()) and int(labels.max()) < self.num_classes):
+            raise ValueError(f"label outside [0, {self.num_classes})")
+        boxes = crop_plan.boxes
+        # one pinned buffer: crop + RandAugment plan | batch plan | host labels
+        n_crop, n_plan = 4 * crop_plan.words(), 4 * plan.words()
+        o_plan = _round_up(n_crop, 16)
+        o_lab = _round_up(o_plan + n_plan, 16)
+        st = self._staging[self._turn]
+        self._turn ^= 1
+        host = st.take(o_lab + (0 if labels.is_cuda else 8 * B))
+        hv = host.numpy()
+        crop_plan.pack(hv[:n_crop].view(np.int32))
+        plan.pack(hv[o_plan:o_plan + n_plan].view(np.int32))
+        if not labels.is_cuda:
+            hv[o_lab:o_lab + 8 * B].view(np.int64)[:] = labels.numpy()
+        with torch.cuda.device(self.device):
+            dev = host.to(self.device, non_blocking=True)
+            st.event = torch.cuda.Event()
+            st.event.record()
+            n_box = 4 * sp.CROP_PLAN_PER_IMAGE * B
+            crop_d = dev[:n_box].view(torch.int32)
+            ra_d = dev[n_box:n_crop].view(torch.int32)
+            plan_d = dev[o_plan:o_plan + n_plan].view(torch.int32)
+            labels_d = labels if labels.is_cuda else dev[o_lab:o_lab + 8 * B].view(torch.int64)
+            u8 = sp.resized_crop(pix_d, offs_d, hw_d, crop_d, self.image_size, crop_plan.kmax(), int(boxes[:, 2].max()),
+                                 int(boxes[:, 3].max()), host=(offs, sizes, boxes))
+            sp.randaugment(u8, ra_d, crop_plan.num_ops)
+            mixed = plan.mode != MODE_NONE
+            out, targets = sp.train_batch_aug(u8, labels_d, self.lut, plan_d, self.num_classes, self.dtype, mixed,
+                                              channels_last=True)
+        if mixed:
+            return out, targets
+        return out, (labels_d if labels.is_cuda else labels_d.clone())
+
     def __call__(self, images: Sequence, labels, crop_plan: Optional[CropAugPlan] = None,
                  plan: Optional[AugPlan] = None):
+        if len(images) and any(_is_encoded(im) for im in images):
+            return self._call_encoded(images, labels, crop_plan, plan)
         arrs = [_as_rgb_u8(im) for im in images]
         B = len(arrs)
         OH, OW = self.image_size

@@ -158,6 +158,10 @@ _SIGS = {
     # training input: crop / flip (eval.hip) and RandAugment (randaug.hip)
     "sdp_resized_crop": ([_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp], _i32),
     "sdp_randaugment": ([_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp], _i32),
+    # hybrid JPEG decode: host Huffman (jpeg_host.hip), device reconstruction (jpeg.hip)
+    "sdp_jpeg_probe": ([_vp, _i64, _vp], _i32),
+    "sdp_jpeg_entropy_decode": ([_vp, _i64, _vp, _i64, _vp, _vp], _i32),
+    "sdp_jpeg_reconstruct": ([_vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp], _i32),
 }
 
 _lib = None
@@ -1605,3 +1609,85 @@ def randaugment(images: torch.Tensor, plan: torch.Tensor, num_ops: int, scratch:
                                scratch.data_ptr(), _stream(out))
     _check(rc, "randaugment")
     return out
+
+
+# ---- hybrid JPEG decode (layouts and codes: include/sdpnet_hip.h) ----
+JPEG_INFO_WORDS = 16
+JPEG_DESC_WORDS = 64      # int32 words per image: 16 header words, then the 192 bytes of qt
+JPEG_DESC_QT = 16
+JPEG_MALFORMED = {-1: "truncated", -2: "syntax", -3: "code not in its Huffman table", -4: "coefficient index past 63",
+                  -5: "coefficient category", -6: "undefined table", -7: "restart marker", -8: "no EOI",
+                  -9: "coefficient buffer too small", -10: "bad argument"}
+
+
+def _u8_view(data):
+    """A zero-copy uint8 view of a bytes-like object (the caller keeps ``data`` alive)."""
+    import numpy as np
+    a = data if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+    _req(a.dtype == np.uint8 and a.ndim == 1 and a.flags.c_contiguous, "jpeg data: contiguous bytes")
+    return a
+
+
+def jpeg_probe(data) -> Tuple[int, "np.ndarray"]:
+    """(code, info int32 [16]) of one encoded JPEG: markers only (sdp_jpeg_probe).  code 0: taken,
+    > 0: well-formed but outside the subset, < 0: ``JPEG_MALFORMED``."""
+    import numpy as np
+    a = _u8_view(data)
+    info = np.zeros(JPEG_INFO_WORDS, np.int32)
+    rc = lib().sdp_jpeg_probe(a.ctypes.data, a.size, info.ctypes.data)
+    return rc, info
+
+
+def jpeg_entropy_decode(data, coef, qt) -> Tuple[int, "np.ndarray"]:
+    """Huffman-decode one JPEG on the host (sdp_jpeg_entropy_decode; the GIL is released for the
+    call): coef int16 [capacity] and qt uint8 [192] are contiguous numpy arrays the call fills.
+    Returns (code, info)."""
+    import numpy as np
+    a = _u8_view(data)
+    _req(coef.dtype == np.int16 and coef.ndim == 1 and coef.flags.c_contiguous and coef.flags.writeable,
+         "jpeg coef int16 [n]")
+    _req(qt.dtype == np.uint8 and qt.ndim == 1 and qt.size >= 192 and qt.flags.c_contiguous and qt.flags.writeable,
+         "jpeg qt uint8 [192]")
+    info = np.zeros(JPEG_INFO_WORDS, np.int32)
+    rc = lib().sdp_jpeg_entropy_decode(a.ctypes.data, a.size, coef.ctypes.data, coef.size, qt.ctypes.data,
+                                       info.ctypes.data)
+    return rc, info
+
+
+def jpeg_fill_desc(desc_row, info, coef_off: int, ws_off: int, pix_off: int):
+    """Write the 16 header words of one image's descriptor (int32 numpy [64]; the qt bytes behind
+    them are sdp_jpeg_entropy_decode's) from its info words and its three offsets."""
+    import numpy as np
+    desc_row[0:4] = info[0:4]          # W, H, components, mode
+    desc_row[4:6] = info[12:14]        # MCU columns, rows
+    desc_row[6:12].view(np.int64)[:] = (coef_off, ws_off, pix_off)
+    desc_row[12:JPEG_DESC_QT] = 0
+
+
+def jpeg_reconstruct(coef: torch.Tensor, desc_host, desc_dev: torch.Tensor, B: int, ws: torch.Tensor,
+                     pix: torch.Tensor, ws_bytes: Optional[int] = None, pix_bytes: Optional[int] = None):
+    """Dequantise + IDCT + chroma upsampling + colour conversion of B images (sdp_jpeg_reconstruct).
+
+    coef: int16 device tensor; desc_host: int32 numpy [B * 64]; desc_dev: the same words on the
+    device; ws / pix: uint8 device tensors (``ws_bytes`` / ``pix_bytes``: the lengths to state, their
+    sizes when None).  The library checks every image's ranges on desc_host before any launch and
+    raises ValueError otherwise."""
+    import numpy as np
+    _need_cuda(coef, desc_dev, ws, pix)
+    B = int(B)
+    _req(coef.dtype == torch.int16 and coef.dim() == 1 and coef.is_contiguous(), "jpeg coef int16 [n]")
+    _req(isinstance(desc_host, np.ndarray) and desc_host.dtype == np.int32 and desc_host.flags.c_contiguous
+         and desc_host.size >= B * JPEG_DESC_WORDS, "jpeg desc_host int32 [B, 64]")
+    _req(desc_dev.dtype == torch.int32 and desc_dev.is_contiguous() and desc_dev.numel() >= B * JPEG_DESC_WORDS,
+         "jpeg desc_dev int32 [B, 64]")
+    _req(ws.dtype == torch.uint8 and ws.is_contiguous() and pix.dtype == torch.uint8 and pix.is_contiguous(),
+         "jpeg ws / pix uint8")
+    ws_bytes = ws.numel() if ws_bytes is None else int(ws_bytes)
+    pix_bytes = pix.numel() if pix_bytes is None else int(pix_bytes)
+    _req(0 <= ws_bytes <= ws.numel() and 0 <= pix_bytes <= pix.numel(), "jpeg stated lengths")
+    rc = lib().sdp_jpeg_reconstruct(coef.data_ptr(), coef.numel(), desc_host.ctypes.data, desc_dev.data_ptr(), B,
+                                    ws.data_ptr(), ws_bytes, pix.data_ptr(), pix_bytes, _stream(pix))
+    if rc == 1:
+        raise ValueError("sdpnet HIP op: invalid arguments (jpeg_reconstruct: a descriptor leaves the buffers given)")
+    _check(rc, "jpeg_reconstruct")
+    return pix
