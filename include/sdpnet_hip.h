@@ -309,11 +309,17 @@ int sdp_dwconv(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_gstri
                const float* weight, const float* bias, void* Y, int64_t ldy, int y_grp,
                int64_t y_gstride, int y_off, int B, int H, int W, int C, int k, void* stream);
 /* Select the depthwise kernel: 3 (default) = MFMA Toeplitz form
- * (bf16, C % 32 == 0, H, W <= 16, k in {3,5,7}), 2 = 64-channel x band blocks with an fp32 LDS tile
+ * (bf16, C % 32 == 0, k in {3,5,7}: one 16 x 16 plane per image for H, W <= 16, 16 x 16 output tiles
+ * with their halo above that where the tiles are at least 9/16 full (49/64 for k = 3), the class
+ * measured faster than 2; same rounding points), 2 = 64-channel x band blocks with an fp32 LDS tile
  * (C % 8 == 0, k in {3,5,7}, 16-B aligned rows), 1 = 32-channel blocks with a
  * bf16 tile (any shape); each falls back to the next where it does not apply.  0 queries; any other
  * value returns -1 and leaves the selection unchanged.  Returns the previous selection. */
 int sdp_dwconv_set_kernel(int k);
+/* The kernel sdp_dwconv runs for 16-B aligned dense operands under the current selection: 1, 2,
+ * 3 (the MFMA form, H, W <= 16) or 5 (the tiled MFMA form, H > 16 or W > 16); -1 for a dtype, size
+ * or k that sdp_dwconv refuses.  Pure: no launch and no device query. */
+int sdp_dwconv_variant(int dtype, int H, int W, int C, int k);
 
 /*
  * softmax(LN_q(Q) LN_k(K)^T / sqrt(hd) + mask) V per (batch, head) from fused QKV
@@ -592,8 +598,14 @@ int sdp_softmax_bwd(int dtype, const void* P, int64_t ldp, const void* DPd, int6
 
 /* Depthwise-conv weight gradient (layers.py:73-78): part[chunk][c][t] = sum over the chunk's
  * images of DY[b, h, w, c] * A[b, h + ty - k/2, w + tx - k/2, c] (zero padded), NHWC rows,
- * chunk < sdp_dw_wgrad_chunks(B); H * W <= 640 (both planes staged as fp32), any W, odd k <= 9.  The input gradient is
- * sdp_dwconv with the kernel flipped. */
+ * chunk < sdp_dw_wgrad_chunks(B); odd k <= 9.  Any H x W whose staging fits: up to H * W = 640
+ * both planes of an image are staged whole as fp32 (one kernel, unchanged results); a larger
+ * plane is walked in bands of output rows (band rows of DY, band + k - 1 rows of A, at most
+ * 64 KiB where one row fits that, else at most 160 KiB), which needs one DY row with its k A rows
+ * in 160 KiB: W <= 1280 / (k + 1) (160, 213, 320 at k = 7, 5, 3; 128 at k = 9).  A wider plane
+ * above 640 pixels returns hipErrorInvalidValue before any launch and leaves part untouched.
+ * The order of additions is a function of (B, H, W, k) alone.  The input gradient is sdp_dwconv
+ * with the kernel flipped. */
 int sdp_dw_wgrad_chunks(int B);
 int sdp_dw_wgrad(int dtype, const void* A, int64_t lda, int a_grp, int64_t a_gstride, int a_off, const void* DY,
                  int64_t lddy, int dy_grp, int64_t dy_gstride, int dy_off, int B, int H, int W, int C, int k,

@@ -1034,8 +1034,203 @@ static int launch_dw3(int k, const void* X, int64_t ldx, RowMap xm, const float*
   return SDP_CHECK_LAUNCH();
 }
 
+// ---------------------------------------------------------------------------
+// dwconv3t_mfma — dwconv3_mfma for H > 16 or W > 16: the unit of work is (image, 16 x 16 output
+// tile) instead of (image).  The plane buffer, the B fragments, the MFMA section and the rounding
+// points are dwconv3_mfma's: plane[r][q] holds LN(x)[h0 + r - PAD][w0 + q - PAD] of the tile at
+// (h0, w0).  Every cell of the tile and its halo is written per tile, zero where it lies outside
+// the image (those cells change from tile to tile); the columns past the halo are zeroed once and
+// meet only zero rows of B.  A workgroup (32 channels) walks a contiguous range of units, so the
+// tiles of one image follow each other and their halo re-reads hit L2; the next unit's loads are
+// in flight (registers) while the current one computes.  The store is masked to the image.
+// ---------------------------------------------------------------------------
+template <int KS, bool LN>
+__global__ __launch_bounds__(1024) void dwconv3t_mfma(
+    const bf16_t* __restrict__ X, int64_t ldx, RowMap xm, const float* __restrict__ stats,
+    const float* __restrict__ lg, const float* __restrict__ lb, const float* __restrict__ Wt,
+    const float* __restrict__ bias, bf16_t* __restrict__ Y, int64_t ldy, RowMap ym, int B, int H, int W, int C,
+    int ncg, int upb, int nunits, int ntx, int nty) {
+  constexpr int NT = 1024, PAD = KS / 2, TW = 16 + KS - 1;
+  constexpr int CPW = DW3_CB / (NT / 64);          // channels per wave
+  constexpr int NIT = (TW * TW * 4 + NT - 1) / NT;  // staging items per thread (TW x TW cells x 4 parts)
+  __shared__ __attribute__((aligned(16))) bf16_t planes[DW3_CB * DW3_PLANE + 48];
+  __shared__ __attribute__((aligned(16))) bf16_t outs[256 * DW3_CB];  // [tile pixel][32]
+  __shared__ __attribute__((aligned(16))) float lnp[2 * DW3_CB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // block -> (unit, half) as in dwconv3_mfma: the two 32-channel halves of a 64-channel group on one XCD
+  const int xb = blockIdx.x, xcd = xb & 7, kb = xb >> 3;
+  const int unit = xcd + 8 * (kb >> 1), half = kb & 1;
+  if (unit >= nunits) return;
+  const int cgp = unit % ((ncg + 1) / 2), chunk = unit / ((ncg + 1) / 2);
+  const int cg = 2 * cgp + half;
+  if (cg >= ncg) return;
+  const int c0 = cg * DW3_CB;
+  const int T = ntx * nty;
+  const int u0 = chunk * upb, u1 = min(B * T, u0 + upb);
+  if (u0 >= u1) return;
+  const int P = H * W;
+
+  for (int i = tid; i < (DW3_CB * DW3_PLANE + 48) / 8; i += NT) ((bf16x8*)planes)[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+  if (LN && tid < 2 * DW3_CB) lnp[tid] = tid < DW3_CB ? lg[c0 + tid] : lb[c0 + tid - DW3_CB];
+  bf16_t* wl = outs;  // [32 ch][KS][32], tap kx at column kx + 16
+  for (int i = tid; i < DW3_CB * KS * 32; i += NT) {
+    const int cl = i / (KS * 32), r = i - cl * KS * 32, ky = r >> 5, col = r & 31;
+    const int kx = col - 16;
+    wl[i] = (kx >= 0 && kx < KS) ? f2bf(Wt[(int64_t)(c0 + cl) * KS * KS + ky * KS + kx]) : (bf16_t)0;
+  }
+  __syncthreads();
+  const int n = lane & 15, j = lane >> 4;
+  bf16x8 bfr[CPW][KS];
+#pragma unroll
+  for (int cc = 0; cc < CPW; ++cc) {
+    const int cl = CPW * wave + cc;
+#pragma unroll
+    for (int ky = 0; ky < KS; ++ky) {
+      const bf16_t* row = wl + (cl * KS + ky) * 32;
+      u32x4 o;
+#pragma unroll
+      for (int i = 0; i < 8; i += 2) {
+        const int c0i = min(16 + 8 * j - n + i, 31), c1i = min(16 + 8 * j - n + i + 1, 31);
+        o[i >> 1] = (uint32_t)row[c0i] | ((uint32_t)row[c1i] << 16);
+      }
+      bfr[cc][ky] = __builtin_bit_cast(bf16x8, o);
+      asm volatile("" : "+v"(bfr[cc][ky]));
+    }
+  }
+  __syncthreads();  // weights consumed before outs is reused
+
+  // staging role: item t -> halo cell t / 4 = (r, c) of TW x TW, channels 8 * (t & 3) .. +7
+  int dsto[NIT], rr[NIT], rc[NIT];
+#pragma unroll
+  for (int it = 0; it < NIT; ++it) {
+    const int t = tid + NT * it, cell = t >> 2, q = t & 3;
+    const int r = cell / TW, c = cell - r * TW;
+    dsto[it] = cell < TW * TW ? (8 * q) * DW3_PLANE + 16 * q + r * DW3_RS + c : -1;
+    rr[it] = r - PAD;
+    rc[it] = c - PAD;
+  }
+  const int q8 = 8 * (tid & 3);
+  bf16x8 pv[NIT];
+  float2 ps[NIT];
+  uint32_t pin = 0;  // bit it: the item's cell lies inside the image
+  auto load = [&](int u) {
+    const int b = u / T, t = u - b * T, tyy = t / ntx, h0 = 16 * tyy, w0 = 16 * (t - tyy * ntx);
+    const int64_t r0 = xm((int64_t)b * P);
+    pin = 0;
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      const int gh = h0 + rr[it], gw = w0 + rc[it];
+      const bool in = dsto[it] >= 0 && gh >= 0 && gh < H && gw >= 0 && gw < W;
+      const int pix = in ? gh * W + gw : 0;
+      pv[it] = *(const bf16x8*)(X + (r0 + pix) * ldx + c0 + q8);  // unconditional: a static count in flight
+      if constexpr (LN) ps[it] = *(const float2*)(stats + 2 * ((int64_t)b * P + pix));
+      pin |= (uint32_t)in << it;
+    }
+  };
+  auto put = [&]() {  // LN + transpose into the planes; zeros outside the image
+#pragma unroll
+    for (int it = 0; it < NIT; ++it) {
+      if (dsto[it] < 0) continue;
+      bf16_t* dst = planes + dsto[it];
+      const bool in = (pin >> it) & 1;
+      if constexpr (LN) {
+        const f32x4 g0 = *(const f32x4*)(lnp + q8), g1 = *(const f32x4*)(lnp + q8 + 4);
+        const f32x4 e0 = *(const f32x4*)(lnp + DW3_CB + q8), e1 = *(const f32x4*)(lnp + DW3_CB + q8 + 4);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const float x = (bf2f((bf16_t)pv[it][e]) - ps[it].x) * ps[it].y;
+          const float y = e < 4 ? fmaf(x, g0[e], e0[e]) : fmaf(x, g1[e - 4], e1[e - 4]);
+          dst[e * DW3_PLANE] = in ? f2bf(y) : (bf16_t)0;
+        }
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) dst[e * DW3_PLANE] = in ? (bf16_t)pv[it][e] : (bf16_t)0;
+      }
+    }
+  };
+  float bch[CPW];
+#pragma unroll
+  for (int cc = 0; cc < CPW; ++cc) bch[cc] = bias ? bias[c0 + CPW * wave + cc] : 0.f;
+  // store role: tile pixel tid / 4 = (h, w) of 16 x 16, 16-B chunk tid & 3
+  const int sp = tid >> 2, sh = sp >> 4, sw = sp & 15;
+  const int souto = sp * DW3_CB + (((tid & 3) ^ ((sp >> 2) & 3)) << 3);
+  load(u0);
+  put();
+  for (int u = u0; u < u1; ++u) {
+    __syncthreads();  // planes of unit u complete
+    load(min(u + 1, u1 - 1));
+#pragma unroll
+    for (int pp = 0; pp < CPW / 2; ++pp) {
+      f32x4 d[2];
+#pragma unroll
+      for (int c2 = 0; c2 < 2; ++c2) {
+        const int cc = 2 * pp + c2, cl = CPW * wave + cc;
+        const bf16_t* pl = planes + (size_t)cl * DW3_PLANE + 16 * (cl >> 3);
+        d[c2] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ky = 0; ky < KS; ++ky) {
+          const bf16x8 a = *(const bf16x8*)(pl + (n + ky) * DW3_RS + 8 * j);  // A_ky[h = n][8j ..]
+          d[c2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bfr[cc][ky], d[c2], 0, 0, 0);
+        }
+      }
+      // D[h = 4j + i][w = n] -> outs[tile pixel][32], 16-B chunk c of pixel p at c ^ ((p >> 2) & 3)
+      const int cl0 = CPW * wave + 2 * pp;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int p = (4 * j + i) * 16 + n;
+        *(uint32_t*)(outs + p * DW3_CB + (((cl0 >> 3) ^ ((p >> 2) & 3)) << 3) + (cl0 & 7)) =
+            pack_bf16x2(d[0][i] + bch[2 * pp], d[1][i] + bch[2 * pp + 1]);
+      }
+      asm volatile("" ::: "memory");
+    }
+    __syncthreads();  // outs complete; everyone done reading the planes
+    {
+      const int b = u / T, t = u - b * T, tyy = t / ntx;
+      const int gh = 16 * tyy + sh, gw = 16 * (t - tyy * ntx) + sw;
+      if (gh < H && gw < W)
+        *(bf16x8*)(Y + (ym((int64_t)b * P) + gh * W + gw) * ldy + c0 + q8) = *(const bf16x8*)(outs + souto);
+    }
+    if (u + 1 < u1) put();
+  }
+}
+
+static int launch_dw3t(int k, const void* X, int64_t ldx, RowMap xm, const float* stats, const float* lg,
+                       const float* lb, const float* Wt, const float* bias, void* Y, int64_t ldy, RowMap ym, int B,
+                       int H, int W, int C, hipStream_t s) {
+  const int ncg = C / DW3_CB, ntx = (W + 15) / 16, nty = (H + 15) / 16;
+  if ((int64_t)B * ntx * nty > INT32_MAX / 2) return -1;
+  const int U = B * ntx * nty;
+  int dev = 0, ncu = 256;
+  (void)hipGetDevice(&dev);
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || ncu <= 0) ncu = 256;
+  const int npairs = (ncg + 1) / 2;
+  int nchunk = (ncu / 2) / npairs;  // one workgroup per CU, as dwconv3_mfma
+  if (nchunk < 1) nchunk = 1;
+  if (nchunk > U) nchunk = U;
+  const int upb = (U + nchunk - 1) / nchunk;
+  nchunk = (U + upb - 1) / upb;
+  const int nunits = npairs * nchunk;
+  const int grid = ((nunits + 7) / 8) * 16;
+#define SDP_DW3T(KS)                                                                                              \
+  if (stats)                                                                                                      \
+    hipLaunchKernelGGL((dwconv3t_mfma<KS, true>), dim3(grid), dim3(1024), 0, s, (const bf16_t*)X, ldx, xm, stats, \
+                       lg, lb, Wt, bias, (bf16_t*)Y, ldy, ym, B, H, W, C, ncg, upb, nunits, ntx, nty);            \
+  else                                                                                                            \
+    hipLaunchKernelGGL((dwconv3t_mfma<KS, false>), dim3(grid), dim3(1024), 0, s, (const bf16_t*)X, ldx, xm,       \
+                       stats, lg, lb, Wt, bias, (bf16_t*)Y, ldy, ym, B, H, W, C, ncg, upb, nunits, ntx, nty)
+  switch (k) {
+    case 3: SDP_DW3T(3); break;
+    case 5: SDP_DW3T(5); break;
+    case 7: SDP_DW3T(7); break;
+    default: return -1;
+  }
+#undef SDP_DW3T
+  return SDP_CHECK_LAUNCH();
+}
+
 // Highest kernel tier allowed (each tier falls back to the next lower one per shape):
-// 3 (default) = dwconv3_mfma where it applies (bf16, H, W <= 16, C % 32 == 0, k in {3,5,7}),
+// 3 (default) = an MFMA kernel where one applies (bf16, C % 32 == 0, k in {3,5,7}): dwconv3_mfma
+// for H, W <= 16, the tiled dwconv3t_mfma above that for the shape class of dw3t_takes,
 // 2 = dwconv2_nhwc (C % 8 == 0, 16-B rows), 1 = dwconv_ln_nhwc (any shape)
 // An unknown tier returns -1 and leaves the selection unchanged (0 queries it).
 static int g_dw_kernel = 3;
@@ -1045,6 +1240,37 @@ extern "C" int sdp_dwconv_set_kernel(int k) {
   if (k < 1 || k > 3) return -1;
   g_dw_kernel = k;
   return old;
+}
+
+// The tiled MFMA kernel's shape class under the current selection.  Its time goes with the number
+// of 16 x 16 tiles, dwconv2_nhwc's with the pixels, so the class is bounded by how full the tiles
+// are: routed where it was measured wholly below dwconv2_nhwc (C 768, B 64, alternating windows,
+// profiles/highres.md) -- k = 5, 7 from 24 x 24 (9/16 of the tiles' pixels: 1.17x, 2.0x) up, k = 3
+// from 28 x 28 (49/64: 1.02-1.07x) up; k = 3 at 24 x 24 lost (0.85-0.90x) and emptier tiles were
+// not measured: those stay on dwconv2_nhwc.
+static bool dw3t_takes(int dtype, int H, int W, int C, int k) {
+  if (!(g_dw_kernel >= 3 && dtype == 1 && C % 32 == 0 && (H > 16 || W > 16) && (k == 3 || k == 5 || k == 7)))
+    return false;
+  const int64_t ntiles = (int64_t)((H + 15) / 16) * ((W + 15) / 16);
+  return (int64_t)H * W >= (k == 3 ? 196 : 144) * ntiles;
+}
+
+// whether dwconv2_nhwc's LDS band holds at least one output row of a W-wide image (launch_dw2)
+static bool dw2_fits(int W, int k) {
+  const int strip = W % 8 == 0 ? 8 : 7, pitch = (W + strip - 1) / strip * strip + k - 1;
+  return (int)((DW2_LDS - (size_t)k * k * DW2_CB * 4) / ((size_t)pitch * DW2_CB * 4)) - (k - 1) >= 1;
+}
+
+// The kernel sdp_dwconv runs for 16-B aligned dense operands under the current selection:
+// 1 = dwconv_ln_nhwc, 2 = dwconv2_nhwc, 3 = dwconv3_mfma, 5 = dwconv3t_mfma; -1 for arguments
+// sdp_dwconv refuses.  Pure: no launch, no device query.
+extern "C" int sdp_dwconv_variant(int dtype, int H, int W, int C, int k) {
+  if ((dtype != 0 && dtype != 1) || H <= 0 || W <= 0 || C <= 0 || (k != 1 && k != 3 && k != 5 && k != 7 && k != 9)) return -1;
+  const bool k357 = k == 3 || k == 5 || k == 7;
+  if (g_dw_kernel >= 3 && dtype == 1 && C % 32 == 0 && H <= 16 && W <= 16 && k357) return 3;
+  if (dw3t_takes(dtype, H, W, C, k)) return 5;
+  if (g_dw_kernel >= 2 && C % 8 == 0 && k357 && dw2_fits(W, k)) return 2;
+  return 1;
 }
 
 extern "C" int sdp_dwconv(int dtype, const void* X, int64_t ldx, int x_grp, int64_t x_gstride, int x_off,
@@ -1067,6 +1293,10 @@ extern "C" int sdp_dwconv(int dtype, const void* X, int64_t ldx, int x_grp, int6
   if (g_dw_kernel >= 3 && dtype == 1 && C % 32 == 0 && H <= 16 && W <= 16 && v16 && (k == 3 || k == 5 || k == 7) &&
       ((uintptr_t)weight % 4 == 0)) {
     const int rc = launch_dw3(k, X, ldx, xm, stats, ln_gamma, ln_beta, weight, bias, Y, ldy, ym, B, H, W, C, s);
+    if (rc != -1) return rc;
+  }
+  if (dw3t_takes(dtype, H, W, C, k) && v16 && ((uintptr_t)weight % 4 == 0)) {
+    const int rc = launch_dw3t(k, X, ldx, xm, stats, ln_gamma, ln_beta, weight, bias, Y, ldy, ym, B, H, W, C, s);
     if (rc != -1) return rc;
   }
   // dwconv2_nhwc reads the bias as f32x4

@@ -2062,6 +2062,133 @@ __global__ __launch_bounds__(64 * KS) void dw_wgrad_k(const T* __restrict__ A, i
   for (int tx = 0; tx < KS; ++tx) o[KS * KS + tx] = acc[tx].y;
 }
 
+// The same sum for a plane that does not fit LDS whole (H * W > 640): each image is walked in bands
+// of `band` output rows.  Per band the block stages the band's DY rows [h0, h0 + band) and the A
+// rows [h0 - P, h0 + band + P) as fp32 [pixel][32]; A rows outside the image are zero and the
+// compute skips them, DY rows past the image are neither staged nor read.  The rows of a band that
+// lie inside the image are one contiguous pixel range, so staging needs no division by W.  Thread
+// roles, accumulators (kept across bands and images), the final reduction and the part layout are
+// dw_wgrad_k's; the order of additions depends on (B, H, W, KS) and the band alone.
+template <typename T, int KS>
+__global__ __launch_bounds__(64 * KS) void dw_wgrad_band_k(const T* __restrict__ A, int64_t lda, RowMap am,
+                                                           const T* __restrict__ DY, int64_t lddy, RowMap dym, int B,
+                                                           int H, int W, int C, int ipb, int band,
+                                                           float* __restrict__ part) {
+  extern __shared__ __attribute__((aligned(16))) char dw_sm[];
+  constexpr int P = KS / 2, MW = 16, NT = 64 * KS, U = 4, CB = 32, NCP = CB / 2, NRG = 64 / NCP, CH = CB / 8;
+  const int HW = H * W, RA = band + KS - 1;
+  float* ap = (float*)dw_sm;   // [RA * W][32], local row r is image row h0 - P + r
+  float* dp = ap + RA * W * CB;  // [band * W][32], local row r is image row h0 + r
+  const int c0 = blockIdx.x * CB, chunk = blockIdx.y;
+  const int cp = threadIdx.x % NCP, rg = (threadIdx.x & 63) / NCP, ty = threadIdx.x / 64;
+  f32x2 acc[KS];
+#pragma unroll
+  for (int i = 0; i < KS; ++i) acc[i] = f32x2{0.f, 0.f};
+  const int b0 = chunk * ipb, b1 = min(B, b0 + ipb);
+  const bool v8 = (sizeof(T) == 2) && (c0 + CB <= C) && (lda % 8 == 0) && (lddy % 8 == 0) &&
+                  (((uintptr_t)A & 15) == 0) && (((uintptr_t)DY & 15) == 0);
+  for (int b = b0; b < b1; ++b) {
+    for (int h0 = 0; h0 < H; h0 += band) {
+      const int nr = min(band, H - h0);                          // DY rows of this band
+      const int ga0 = max(h0 - P, 0), ga1 = min(h0 + nr + P, H);  // A rows inside the image
+      const int lo = (ga0 - (h0 - P)) * W, na = (ga1 - ga0) * W, nd = nr * W;  // pixels
+      const int64_t ma = (int64_t)b * HW + ga0 * W, md = (int64_t)b * HW + h0 * W;
+      __syncthreads();
+      if (v8) {  // 16-B loads over the A range then the DY range, U in flight per thread
+        const int n_a = na * CH, n = n_a + nd * CH;
+        for (int e0 = threadIdx.x; e0 < n; e0 += NT * U) {
+          bf16x8 v[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const int e = min(e0 + u * NT, n - 1);
+            const bool ia = e < n_a;
+            const int ee = ia ? e : e - n_a;
+            const T* src = ia ? A + am(ma + ee / CH) * lda : DY + dym(md + ee / CH) * lddy;
+            v[u] = *(const bf16x8*)(src + c0 + (ee % CH) * 8);
+          }
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * NT;
+            if (e < n) {
+              const bool ia = e < n_a;
+              const int ee = ia ? e : e - n_a;
+              f32x4* pd = (f32x4*)((ia ? ap + lo * CB : dp) + (ee / CH) * CB + (ee % CH) * 8);
+              pd[0] = f32x4{bf2f((bf16_t)v[u][0]), bf2f((bf16_t)v[u][1]), bf2f((bf16_t)v[u][2]), bf2f((bf16_t)v[u][3])};
+              pd[1] = f32x4{bf2f((bf16_t)v[u][4]), bf2f((bf16_t)v[u][5]), bf2f((bf16_t)v[u][6]), bf2f((bf16_t)v[u][7])};
+            }
+          }
+        }
+      } else {
+        for (int e = threadIdx.x; e < (na + nd) * CB; e += NT) {
+          const bool ia = e < na * CB;
+          const int ee = ia ? e : e - na * CB;
+          const int px = ee / CB, c = c0 + (ee % CB);
+          float* dst = (ia ? ap + lo * CB : dp) + ee;
+          if (ia)
+            *dst = c < C ? to_f<T>(A[am(ma + px) * lda + c]) : 0.f;
+          else
+            *dst = c < C ? to_f<T>(DY[dym(md + px) * lddy + c]) : 0.f;
+        }
+      }
+      // zero the A rows outside the image: local pixels [0, lo) and [lo + na, RA * W)
+      const int nz = RA * W - na;
+      for (int e = threadIdx.x; e < nz * (CB / 4); e += NT) {
+        const int z = e / (CB / 4), px = z < lo ? z : z + na;
+        ((f32x4*)(ap + px * CB))[e % (CB / 4)] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      __syncthreads();
+      for (int hl = rg; hl < nr; hl += NRG) {
+        const int hh = h0 + hl + ty - P, ra = hl + ty;  // image row and local row of A
+        if (hh < 0 || hh >= H) continue;
+        for (int w0 = 0; w0 < W; w0 += MW) {
+          f32x2 ar[MW + KS - 1], dr[MW];
+#pragma unroll
+          for (int q = 0; q < MW + KS - 1; ++q) {
+            const int ww = w0 + q - P;
+            ar[q] = (ww >= 0 && ww < W) ? *(const f32x2*)(ap + (ra * W + ww) * CB + 2 * cp) : f32x2{0.f, 0.f};
+          }
+#pragma unroll
+          for (int q = 0; q < MW; ++q)
+            dr[q] = w0 + q < W ? *(const f32x2*)(dp + (hl * W + w0 + q) * CB + 2 * cp) : f32x2{0.f, 0.f};
+#pragma unroll
+          for (int q = 0; q < MW; ++q)
+#pragma unroll
+            for (int tx = 0; tx < KS; ++tx) acc[tx] = __builtin_elementwise_fma(dr[q], ar[q + tx], acc[tx]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int tx = 0; tx < KS; ++tx) {
+#pragma unroll
+    for (int sh = NCP; sh < 64; sh *= 2) {
+      acc[tx].x += __shfl_xor(acc[tx].x, sh);
+      acc[tx].y += __shfl_xor(acc[tx].y, sh);
+    }
+  }
+  const int c = c0 + 2 * cp;
+  if (rg || c >= C) return;
+  float* o = part + ((int64_t)chunk * C + c) * (KS * KS) + ty * KS;
+#pragma unroll
+  for (int tx = 0; tx < KS; ++tx) o[tx] = acc[tx].x;
+  if (c + 1 >= C) return;
+#pragma unroll
+  for (int tx = 0; tx < KS; ++tx) o[KS * KS + tx] = acc[tx].y;
+}
+
+// Band of the banded kernel for a W-wide plane: the most rows whose staging (band DY rows and
+// band + k - 1 A rows of W x 128 B) fits 64 KiB, so two workgroups share a CU as above; a band above
+// four rows is cut to a multiple of the four row groups.  Where not even one row fits 64 KiB, the
+// most rows that fit 160 KiB.  0: one DY row with its k A rows does not fit, W * (k + 1) > 1280.
+static int dw_wgrad_band(int H, int W, int k) {
+  if ((int64_t)W * (k + 1) > 1280) return 0;
+  const int r64 = 64 * 1024 / (W * 128), r160 = 160 * 1024 / (W * 128);
+  int band = r64 >= k + 1 ? (r64 - (k - 1)) / 2 : (r160 - (k - 1)) / 2;
+  if (band > H) band = H;
+  if (r64 >= k + 1 && band > 4) band -= band % 4;
+  return band;
+}
+
 extern "C" int sdp_dw_wgrad_chunks(int B) { return B < 64 ? (B > 0 ? B : 1) : 64; }
 
 extern "C" int sdp_dw_wgrad(int dtype, const void* A, int64_t lda, int a_grp, int64_t a_gstride, int a_off,
@@ -2070,8 +2197,11 @@ extern "C" int sdp_dw_wgrad(int dtype, const void* A, int64_t lda, int a_grp, in
   if (!A || !DY || !part || B < 0 || H <= 0 || W <= 0 || C <= 0 || (k != 3 && k != 5 && k != 7 && k != 9))
     return (int)hipErrorInvalidValue;
   if (B == 0) return 0;
-  const size_t lds = (size_t)H * W * 32 * 2 * 4;  // both planes, fp32 [HW][32]
-  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  if ((int64_t)H * W > INT32_MAX) return (int)hipErrorInvalidValue;
+  const bool whole = (int64_t)H * W <= 640;  // both planes fit LDS as fp32 [HW][32]: dw_wgrad_k
+  const int band = whole ? H : dw_wgrad_band(H, W, k);
+  if (band <= 0) return (int)hipErrorInvalidValue;
+  const size_t lds = whole ? (size_t)H * W * 32 * 2 * 4 : (size_t)(2 * band + k - 1) * W * 32 * 4;
   if ((a_grp > 0 && a_grp % (H * W)) || (dy_grp > 0 && dy_grp % (H * W))) return (int)hipErrorInvalidValue;
   const RowMap am = mk_tmap(a_grp, a_gstride, a_off), dym = mk_tmap(dy_grp, dy_gstride, dy_off);
   const int nch = sdp_dw_wgrad_chunks(B), ipb = (B + nch - 1) / nch;
@@ -2079,9 +2209,17 @@ extern "C" int sdp_dw_wgrad(int dtype, const void* A, int64_t lda, int a_grp, in
   hipStream_t s = (hipStream_t)stream;
 #define SDP_DWG(TT, KK)                                                                                              \
   do {                                                                                                               \
-    (void)hipFuncSetAttribute((const void*)dw_wgrad_k<TT, KK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL((dw_wgrad_k<TT, KK>), grid, dim3(64 * KK), lds, s, (const TT*)A, lda, am, (const TT*)DY, lddy, \
-                       dym, B, H, W, C, ipb, part);                                                                  \
+    if (whole) {                                                                                                     \
+      (void)hipFuncSetAttribute((const void*)dw_wgrad_k<TT, KK>, hipFuncAttributeMaxDynamicSharedMemorySize,         \
+                                (int)lds);                                                                           \
+      hipLaunchKernelGGL((dw_wgrad_k<TT, KK>), grid, dim3(64 * KK), lds, s, (const TT*)A, lda, am, (const TT*)DY,    \
+                         lddy, dym, B, H, W, C, ipb, part);                                                          \
+    } else {                                                                                                         \
+      (void)hipFuncSetAttribute((const void*)dw_wgrad_band_k<TT, KK>, hipFuncAttributeMaxDynamicSharedMemorySize,    \
+                                (int)lds);                                                                           \
+      hipLaunchKernelGGL((dw_wgrad_band_k<TT, KK>), grid, dim3(64 * KK), lds, s, (const TT*)A, lda, am,              \
+                         (const TT*)DY, lddy, dym, B, H, W, C, ipb, band, part);                                     \
+    }                                                                                                                \
   } while (0)
 #define SDP_DWG_T(TT)                  \
   switch (k) {                         \

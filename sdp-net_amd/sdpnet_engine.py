@@ -238,3 +238,80 @@ class GraphedForward:
             self._capture()
         self._graph.replay()
         return self._y
+
+
+# ---------------------------------------------------------------------------
+# Moving a checkpoint to another patch grid.  The reference defines no resampling of its position
+# parameters, so this project does: on the CPU in fp64, rounded once to fp32 (then to the stored
+# dtype).  A size that does not change returns the stored tensor itself.
+_DDP_PREFIXES = ("module.", "_orig_mod.")
+
+
+def _resample_table(w: torch.Tensor, n_new: int) -> torch.Tensor:
+    """[n_old, C] -> [n_new, C] along its length: linear, half-pixel centres, edges clamped."""
+    if w.shape[0] == n_new:
+        return w
+    r = F.interpolate(w.detach().cpu().double().t()[None], size=n_new, mode="linear", align_corners=False)
+    return r[0].t().contiguous().float().to(dtype=w.dtype, device=w.device)
+
+
+def _resample_bone(b: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+    """[1, C, H0 + k, W0 + k] -> [1, C, H1 + k, W1 + k]: bicubic, half-pixel centres."""
+    if tuple(b.shape[-2:]) == tuple(size):
+        return b
+    r = F.interpolate(b.detach().cpu().double(), size=tuple(size), mode="bicubic", align_corners=False)
+    return r.float().to(dtype=b.dtype, device=b.device)
+
+
+def resize_positions(state_dict: Dict[str, torch.Tensor], config: dict, max_image_size, *, prefix: str = ""):
+    """(state_dict, config) of the same MainModel at another ``max_image_size``.
+
+    EmbeddingLayer: each of the two tables is resampled along its own length to its own new length
+    (``vertical_*`` is sized by ``max_image_size[0]``, ``horizontal_*``, the one indexed by rows,
+    by ``max_image_size[1]``, as the model has them) and the two ``arange`` buffers are rebuilt.
+    ConvEmbedding: ``bone`` goes to ``[1, C, H1 + k, W1 + k]`` with k the config's
+    ``conv_embedding_kernel_size``.  Every other tensor, the register table and buffers among
+    them, is passed through as the same object.  DDP / torch.compile key prefixes (``module.``,
+    ``_orig_mod.``) are stripped, as eval_harness.preprocess_weights strips them; ``prefix`` names
+    where the model sits inside a larger dict (``"student."``) and is kept.  The result loads with
+    ``strict=True`` into ``MainModel.from_dict(**config)``."""
+    new = [int(max_image_size[0]), int(max_image_size[1])]
+    if new[0] <= 0 or new[1] <= 0:
+        raise ValueError(f"resize_positions: max_image_size {list(max_image_size)} must be positive")
+    k = int(config.get("conv_embedding_kernel_size", 5))
+    emb = prefix + "embedding_layer."
+    sized = {emb + "vertical_embedding_layer.weight": 0, emb + "horizontal_embedding_layer.weight": 1,
+             emb + "vertical_embedding": 0, emb + "horizontal_embedding": 1}
+    out, seen = {}, 0
+    for key, t in state_dict.items():
+        while key.startswith(_DDP_PREFIXES):
+            key = key[len(next(p for p in _DDP_PREFIXES if key.startswith(p))):]
+        if key in sized:
+            n = new[sized[key]]
+            if key.endswith(".weight"):
+                t = _resample_table(t, n)
+            elif t.shape[0] != n:
+                t = torch.arange(n, dtype=t.dtype, device=t.device)
+            seen += 1
+        elif key == emb + "bone":
+            t = _resample_bone(t, (new[0] + k, new[1] + k))
+            seen += 1
+        out[key] = t
+    if seen == 0:
+        raise KeyError(f"resize_positions: no position tensors under {emb!r}")
+    cfg = dict(config)
+    cfg["max_image_size"] = new
+    return out, cfg
+
+
+def with_max_image_size(model: nn.Module, max_image_size) -> nn.Module:
+    """A new MainModel at ``max_image_size`` holding ``model``'s weights with its position
+    parameters resampled (resize_positions); same device, parameter dtype and train/eval mode."""
+    from model import MainModel
+    state, cfg = resize_positions(model.state_dict(), model.config, max_image_size)
+    new = MainModel.from_dict(**cfg)
+    p = next(model.parameters())
+    new = new.to(device=p.device, dtype=p.dtype)
+    new.load_state_dict(state, strict=True)
+    new.train(model.training)
+    return new

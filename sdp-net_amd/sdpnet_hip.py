@@ -68,6 +68,7 @@ _SIGS = {
     "sdp_dwconv": ([_i32, _vp, _i64, *_ROWMAP, _vp, _vp, _vp, _vp, _vp, _vp, _i64, *_ROWMAP, _i32, _i32, _i32,
                     _i32, _i32, _vp], _i32),
     "sdp_dwconv_set_kernel": ([_i32], _i32),
+    "sdp_dwconv_variant": ([_i32, _i32, _i32, _i32, _i32], _i32),
     "sdp_attention": ([_i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i64,
                        _i64, _vp], _i32),
     "sdp_attention_rows": ([_i32, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i64,
@@ -1233,6 +1234,9 @@ def softmax_bwd(P: torch.Tensor, dPd: torch.Tensor, dS: torch.Tensor, rows: int,
 def dw_wgrad(a: Rows, dy: Rows, B: int, H: int, W: int, C: int, k: int) -> torch.Tensor:
     """Depthwise weight gradient [C, k*k] fp32 (reduced over the chunk slabs)."""
     _need_cuda(a.t, dy.t)
+    _req(H * W <= 640 or W * (k + 1) <= 1280,
+         f"dw_wgrad: a {H}x{W} plane at k={k} cannot be staged: above 640 pixels the kernel needs one row of DY "
+         f"and k rows of A in 160 KiB of LDS, W <= 1280 / (k + 1) = {1280 // (k + 1)}")
     nch = lib().sdp_dw_wgrad_chunks(B)
     part = torch.empty(nch, C * k * k, dtype=torch.float32, device=a.t.device)
     rc = lib().sdp_dw_wgrad(dcode(a.t.dtype), *a.args(), *dy.args(), B, H, W, C, k, part.data_ptr(), _stream(part))
